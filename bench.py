@@ -2,8 +2,17 @@
 """Device-resident batched Snappy benchmark (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3-decompress]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch resident in HBM.
+A plain run sets up the batch, warms up, times the K steps and prints the
+result line (metric, value, ms_per_step, config).  `--dump-outputs DIR` also
+writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
+Everything else the benchmark measures or checks runs only with `--full`: the
+oracle spot check and round-trip check (`correct`), the roofline figures, the
+encode leg, the end-to-end legs, the CPU baselines, the multi-GPU all-gather
+and root-scatter, the serial comparison of a pipelined run, and c1-echo's
+other codec modes.  The --no-* switches trim a --full run.
 Default workload (the north-star target config): decompress
 65,536 x 64 KiB Zipf-text bodies; the same run also times C3 compress of the
 same bodies (the `encode` object).  Other workloads: c2-decompress (65,536 x
@@ -95,6 +104,11 @@ def parse(argv=None):
                     help="decompress on a GPU: time a stream of two alternating batches, batch k+1's "
                          "tag walk (pass 1, its own stream) beside batch k's execution "
                          "(fsg_decompress_batch_2s); 0 = one batch, both passes on one stream")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and the secondary measurements (correct, roofline, encode, "
+                         "end_to_end, cpu_baseline, multi_gpu); a plain run times the steps only")
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
 
@@ -318,11 +332,12 @@ def rank_main(args, codec_factory=None):
     _sync(torch, dev)
     comp_len = d_comp_len.cpu().numpy()[:n].view(np.uint32).copy()
     comp_total = int(comp_len.astype(np.uint64).sum())
-    errors = int((d_status[:n] != 0).sum().item())
+    full = args.full
+    errors = int((d_status[:n] != 0).sum().item()) if full else 0
 
     # Oracle spot check of the compressed bytes (checker only, never timed).
     sample_ok = None
-    if args.verify_sample > 0 and n:
+    if full and args.verify_sample > 0 and n:
         sys.path.insert(0, str(REPO / "oracle"))
         from bind import Oracle
         orc = Oracle()
@@ -372,8 +387,9 @@ def rank_main(args, codec_factory=None):
         del d_ws2
         _sync(torch, dev)
         comp_len2 = d_comp2_len.cpu().numpy()[:n].view(np.uint32).copy()
-        errors += int((d_status2 != 0).sum().item())
-        if args.verify_sample > 0:
+        if full:
+            errors += int((d_status2 != 0).sum().item())
+        if full and args.verify_sample > 0:
             idx = np.linspace(0, n - 1, min(n, args.verify_sample)).astype(np.int64)
             host_comp2 = d_comp2.cpu().numpy()
             sample_ok = sample_ok and all(
@@ -399,8 +415,12 @@ def rank_main(args, codec_factory=None):
     if pipe is not None:
         t_step, avg_kernel_s, lat_s = time_pipelined(torch, dev, stream, pipe["slots"], pipe["issue"],
                                                      args.steps, args.warmup, world, dist)
+        if args.dump_outputs:  # the slot the last timed step decoded into
+            _, _, _, o, _, _, ol, st, _ = pipe["slots"][(args.steps - 1) % 2]
+            dump_outputs(torch, args.dump_outputs, rank, world, op, o,
+                         raw_total if args.steps % 2 else pipe["raw2_total"], ol, st, n, None)
         # the same batch, both passes on one stream, for comparison (untimed in `value`)
-        t_serial, k_serial = time_steps(torch, dev, stream, step, args.steps, 1, world, dist)
+        k_serial = time_steps(torch, dev, stream, step, args.steps, 1, world, dist)[1] if full else None
         # both batches' bytes per step pair: the mean over the stream
         algo_bytes = (raw_total + comp_total + pipe["raw2_total"] + pipe["comp2_total"]) / 2
         pipeline_info = {
@@ -408,30 +428,39 @@ def rank_main(args, codec_factory=None):
             "mode": "batch k+1's tag walk (pass 1) on a second stream beside batch k's execution "
                     "(fsg_decompress_batch_2s); one batch in flight ahead",
             "latency_ms_per_batch": round(lat_s * 1e3, 4),
-            "serial_ms_per_step": round(k_serial * 1e3, 4),
+            "serial_ms_per_step": round(k_serial * 1e3, 4) if full else None,
         }
     else:
         t_step, avg_kernel_s = time_steps(torch, dev, stream, step, args.steps, args.warmup, world, dist)
+        if args.dump_outputs:
+            if op == "decompress":
+                dump_outputs(torch, args.dump_outputs, rank, world, op, d_out, raw_total, d_out_len,
+                             d_status, n, None)
+            else:
+                dump_outputs(torch, args.dump_outputs, rank, world, op, d_comp, c_tot, d_comp_len,
+                             d_status, n, c_off)
 
     # Correctness of the timed output (device-side, untimed).
-    errors += int((d_status[:n] != 0).sum().item())
-    if op == "decompress":
-        roundtrip_ok = bool(torch.equal(d_out[:raw_total], d_raw[:raw_total]))
-        if pipe is not None:
-            _, _, _, o2, _, _, _, st2, _ = pipe["slots"][1]
-            errors += int((st2 != 0).sum().item())
-            roundtrip_ok = roundtrip_ok and bool(torch.equal(o2[:pipe["raw2_total"]], pipe["raw2"]))
-    else:
-        roundtrip_ok = bool((d_comp_len.cpu().numpy()[:n].view(np.uint32) == comp_len).all())
+    roundtrip_ok = None
+    if full:
+        errors += int((d_status[:n] != 0).sum().item())
+        if op == "decompress":
+            roundtrip_ok = bool(torch.equal(d_out[:raw_total], d_raw[:raw_total]))
+            if pipe is not None:
+                _, _, _, o2, _, _, _, st2, _ = pipe["slots"][1]
+                errors += int((st2 != 0).sum().item())
+                roundtrip_ok = roundtrip_ok and bool(torch.equal(o2[:pipe["raw2_total"]], pipe["raw2"]))
+        else:
+            roundtrip_ok = bool((d_comp_len.cpu().numpy()[:n].view(np.uint32) == comp_len).all())
 
     # Per-message (out_len, status) of every rank, gathered over RCCL.
     gather = gather_results(torch, dist, dev, world, rank, n, d_out_len, d_status,
-                            batch.lens if op == "decompress" else comp_len) if world > 1 else None
+                            batch.lens if op == "decompress" else comp_len) if full and world > 1 else None
 
     # Root-scatter variant: rank 0 is the only ingress; it sends each peer a
     # compressed shard with grouped send/recv, then every rank decodes.
     rscatter = None
-    if world > 1 and op == "decompress" and not args.no_root_scatter:
+    if full and world > 1 and op == "decompress" and not args.no_root_scatter:
         rscatter = root_scatter(torch, dist, dev, stream, world, rank, codec, d_comp, d_comp_off,
                                 d_comp_len, n, d_raw, d_raw_len, d_raw_off, raw_total, c_tot)
 
@@ -442,32 +471,33 @@ def rank_main(args, codec_factory=None):
         comp_v = (comp_total + pipe["comp2_total"]) // 2
     if world > 1:
         t_step, avg_kernel_s, (raw_all, comp_all, errors, bad) = shard.reduce_measurements(
-            dist, dev, t_step, avg_kernel_s, raw_v, comp_v, errors, int(not roundtrip_ok))
-        roundtrip_ok = bad == 0
+            dist, dev, t_step, avg_kernel_s, raw_v, comp_v, errors, int(full and not roundtrip_ok))
+        roundtrip_ok = bad == 0 if full else None
     else:
         raw_all, comp_all = raw_v, comp_v
 
     # The encode leg of the default decode run (same bodies, already resident).
     enc = None
-    if op == "decompress" and not args.no_encode and args.workload == "c3-decompress" and world == 1:
+    if full and op == "decompress" and not args.no_encode and args.workload == "c3-decompress" and world == 1:
         enc = encode_leg(torch, dev, stream, encode_step, d_comp, d_comp_len, comp_len, raw_total,
                          comp_total, args, batch, c_off)
 
     # End-to-end (host pinned -> device -> kernel -> host pinned), untimed in `value`.
     e2e = None
-    if not args.no_e2e and rank == 0 and gpu:
+    if full and not args.no_e2e and rank == 0 and gpu:
         e2e = end_to_end(torch, codec, op, batch, d_comp, c_off, comp_len, raw_total, comp_total, n,
                          max_len, dev, d_ws)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(op, batch, d_comp, c_off, comp_len, args.cpu_threads)
 
     if rank == 0:
         value = raw_all / t_step / GIB
         achieved = algo_bytes / avg_kernel_s / 1e9
         # PMC traffic is per launch of the full-size workload on one rank's shard
-        pmc = load_traffic(args.workload) if (args.n_msgs == 0 and (scaling == "weak" or world == 1)) else None
+        pmc = (load_traffic(args.workload)
+               if full and args.n_msgs == 0 and (scaling == "weak" or world == 1) else None)
         line = {
             "metric": METRIC,
             "value": round(value, 3),
@@ -481,7 +511,7 @@ def rank_main(args, codec_factory=None):
             "vs_baseline": None,
             "dtype": "u8",
             "data": "synthetic (splitmix64-seeded bodies, SURVEY.md §8(d)); compressed by the GPU "
-                    "encoder, byte-checked against the oracle",
+                    "encoder" + (", byte-checked against the oracle" if full else ""),
             "config": {
                 "workload": desc,
                 "op": op,
@@ -521,7 +551,12 @@ def rank_main(args, codec_factory=None):
             "kernel_src": kernel_source_hash(),
             "kernels": {"decode": args.decode_kernel, "encode": args.encode_kernel},
             "setup_s": round(gen_s, 2),
+            "full": full,
         }
+        if not full:  # a plain run reports the timed steps only
+            line["roofline"] = line["correct"] = line["multi_gpu"] = None
+        if args.dump_outputs:
+            line["outputs"] = str(args.dump_outputs)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
@@ -651,6 +686,60 @@ def load_traffic(workload: str):
         return None
     d = json.loads(p.read_text())
     return d if d.get("kernel_src") == kernel_source_hash() else None
+
+
+DUMP_SAMPLE = 1 << 22  # output bytes sampled by --dump-outputs (all ranks together)
+DUMP_BLOCK = 4096      # bytes per block sum (per rank; times the world size)
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(torch, outdir, rank, world, op, d_buf, total, d_len, d_status, n, slot_off):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files
+    that two builds can compare array for array (the inputs are seeded, so
+    equal arguments give equal arrays).  At most 64 MB over all ranks:
+
+      out_len.npy         float64[n]  per-message output length
+      status.npy          float32[n]  per-message status
+      out_bytes.npy       float32[k]  output bytes at k fixed, seeded positions
+                                      (every byte if the output has at most k)
+      out_block_sums.npy  float64[b]  decompress: byte sum of every block of
+                                      DUMP_BLOCK x world output bytes
+
+    A decompress output is dense (`total` bytes, slot_off None).  A compress
+    output sits in MaxCompressedLength slots at `slot_off`; only the out_len
+    bytes the encoder produced in each slot are sampled.  Ranks of a
+    multi-GPU run write <name>_rank<r>.npy."""
+    out = Path(outdir)
+    out.mkdir(parents=True, exist_ok=True)
+    lens = d_len[:n].cpu().numpy().view(np.uint32).astype(np.int64)
+    rng = np.random.default_rng(DUMP_SEED + rank)
+    k = max(1, DUMP_SAMPLE // world)
+    if slot_off is None:
+        pos = np.arange(total) if total <= k else np.sort(rng.integers(0, total, size=k))
+    else:
+        live = np.flatnonzero(lens > 0)
+        m = np.sort(rng.choice(live, size=k)) if len(live) else live
+        pos = slot_off[m].astype(np.int64) + (rng.random(len(m)) * lens[m]).astype(np.int64)
+    sample = d_buf[torch.from_numpy(pos).to(d_buf.device)].cpu().numpy() if len(pos) else np.zeros(0, np.uint8)
+    arrays = {"out_len": lens.astype(np.float64),
+              "status": d_status[:n].cpu().numpy().astype(np.float32),
+              "out_bytes": sample.astype(np.float32)}
+    if slot_off is None:
+        block = DUMP_BLOCK * world
+        nb = total // block
+        sums = torch.zeros(nb + (1 if total % block else 0), dtype=torch.float64, device=d_buf.device)
+        per = max(1, (1 << 28) // block)  # 256 MiB of output per reduction
+        for b0 in range(0, nb, per):
+            b1 = min(nb, b0 + per)
+            sums[b0:b1] = d_buf[b0 * block:b1 * block].view(-1, block).sum(dim=1, dtype=torch.int64)
+        if total % block:
+            sums[nb] = d_buf[nb * block:total].sum(dtype=torch.int64)
+        arrays["out_block_sums"] = sums.cpu().numpy()
+    nbytes = sum(a.nbytes for a in arrays.values())
+    if nbytes * world > 64_000_000:
+        raise RuntimeError(f"--dump-outputs: {nbytes} bytes per rank x {world} ranks exceeds 64 MB")
+    for name, a in arrays.items():
+        np.save(out / (f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), a)
 
 
 def pack_bodies(torch, d_comp, c_off, comp_len, comp_total):
@@ -925,9 +1014,10 @@ def echo_main(args):
         return json.loads(r.stdout.strip().splitlines()[-1])
 
     main_run = run("runtime", calls)
-    modes = {"gpu": run("gpu", max(1000, calls // 4)), "none": run("none", calls)}
+    # the other codec modes and the reference's Snappy: --full only
+    modes = {"gpu": run("gpu", max(1000, calls // 4)), "none": run("none", calls)} if args.full else {}
     base = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         ref = run("reference", calls)
         base = {"value": ref["qps"], "unit": "QPS", "cores": 1, "kind": "reference",
                 "sample": f"{ref['calls']} echo calls through the reference's snappy.cc (oracle/_ref) on this "
@@ -952,6 +1042,8 @@ def echo_main(args):
 def main(argv=None):
     args = parse(argv)
     if args.workload == "c1-echo":
+        if args.dump_outputs:
+            sys.exit("bench.py: --dump-outputs needs a batch workload; c1-echo returns no arrays")
         echo_main(args)
         return
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:

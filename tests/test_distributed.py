@@ -87,7 +87,7 @@ def _run_bench_launcher(nprocs, extra):
     import sys
     from pathlib import Path
     repo = Path(__file__).resolve().parents[1]
-    argv = ["--device", "cpu", "--gpus", str(nprocs), "--steps", "2", "--warmup", "1", "--no-e2e",
+    argv = ["--full", "--device", "cpu", "--gpus", str(nprocs), "--steps", "2", "--warmup", "1", "--no-e2e",
             "--no-cpu-baseline", "--verify-sample", "4", *extra]
     code = ("import sys; sys.path.insert(0, %r); import bench; "
             "sys.exit(bench.launch(%d, %r, entry=%r, timeout_s=240))"

@@ -19,7 +19,7 @@ import fsg  # noqa: E402
 
 
 def _launch(extra):
-    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-e2e", "--no-cpu-baseline",
+    argv = ["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-e2e", "--no-cpu-baseline",
             "--no-encode", "--pipeline", "0", "--verify-sample", "8", *extra]
     code = ("import sys; sys.path.insert(0, %r); import bench; "
             "sys.exit(bench.launch(2, %r, env_extra={'FSG_BENCH_SHARED_DEVICE': '0'}, timeout_s=150))"

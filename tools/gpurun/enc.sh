@@ -2,7 +2,7 @@
 # Encode variants on C3 compress: v3 at several lane counts (FSG_ENCODE_LANES),
 # and the LDS-table v1 encoder.
 mkdir -p gpurun_out/enc
-B="python bench.py --no-cpu-baseline --no-e2e --steps 3 --warmup 1 --verify-sample 16 --workload c3-compress"
+B="python bench.py --full --no-cpu-baseline --no-e2e --steps 3 --warmup 1 --verify-sample 16 --workload c3-compress"
 run() {  # name env...
   local n=$1; shift
   env "$@" timeout -k 10 300 $B > gpurun_out/enc/$n.json 2> gpurun_out/enc/$n.err || { tail -5 gpurun_out/enc/$n.err; return 1; }

@@ -16,13 +16,13 @@ if [ -z "$SKIP_TESTS" ]; then
   echo smoke ok
 fi
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err \
+  timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err \
     || { tail -20 $O/bench_default.err; exit 1; }
   cat $O/bench_default.json
 fi
 Q="--no-cpu-baseline --no-e2e --no-encode --verify-sample 0"
 for w in ${BENCH_WORKLOADS:-}; do
-  timeout -k 10 300 python bench.py --steps 10 --warmup 2 $Q --workload $w \
+  timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 $Q --workload $w \
     > $O/bench_$w.json 2> $O/bench_$w.err || { tail -20 $O/bench_$w.err; exit 1; }
   python -c "import json;d=json.load(open('$O/bench_$w.json'));print('$w', d['ms_per_step'], d['value'], d['roofline']['frac'])"
 done

@@ -8,7 +8,7 @@ if [ -z "$SKIP_TESTS" ]; then
     > $O/pytest_gpu.log 2>&1 || { tail -30 $O/pytest_gpu.log; exit 1; }
   tail -1 $O/pytest_gpu.log
 fi
-B="python bench.py --no-cpu-baseline --no-e2e --no-encode --steps 20 --warmup 3 --verify-sample 16"
+B="python bench.py --full --no-cpu-baseline --no-e2e --no-encode --steps 20 --warmup 3 --verify-sample 16"
 for pass in 1 2; do
   for cfg in ${CFGS:-"p0" "p1" "p1:FSG_EXEC_PERSIST=0" "p1:FSG_EXEC_PERSIST=0:FSG_LEAN_WALK=0" "p1:FSG_EXEC_PERSIST=5"}; do
     p=${cfg%%:*}; envs=$(echo "${cfg#$p}" | tr ':' ' ')

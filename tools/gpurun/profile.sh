@@ -8,7 +8,7 @@ set -e
 export TMPDIR=/tmp
 O=gpurun_out/prof
 mkdir -p $O
-B="python bench.py"
+B="python bench.py --full"
 timeout -k 10 300 $B > $O/bench_c3d.json 2> $O/bench_c3d.err
 timeout -k 10 300 $B --workload c2-decompress --steps 20 --warmup 3 > $O/bench_c2d.json 2> $O/bench_c2d.err
 timeout -k 10 300 $B --workload cm-decompress --steps 5 --warmup 1 > $O/bench_cmd.json 2> $O/bench_cmd.err
