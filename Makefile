@@ -6,7 +6,7 @@ PKG      := flare-cpp_amd
 LIB      := $(PKG)/lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall
 CSRC     := $(PKG)/csrc/capi.hip $(PKG)/csrc/snappy_decode.hip $(PKG)/csrc/snappy_decode_v3.hip $(PKG)/csrc/snappy_decode_v4.hip $(PKG)/csrc/snappy_decode_partial.hip \
-            $(PKG)/csrc/snappy_encode.hip $(PKG)/csrc/snappy_encode_v3.hip $(PKG)/csrc/snappy_encode_wave.hip $(PKG)/csrc/gather.hip $(PKG)/csrc/lz4.hip $(PKG)/csrc/lz4_decode2.hip
+            $(PKG)/csrc/snappy_encode.hip $(PKG)/csrc/snappy_encode_v3.hip $(PKG)/csrc/snappy_encode_wave.hip $(PKG)/csrc/gather.hip $(PKG)/csrc/pack.hip $(PKG)/csrc/lz4.hip $(PKG)/csrc/lz4_decode2.hip
 CHDRS    := $(PKG)/csrc/options.h $(PKG)/csrc/snappy_device.h $(PKG)/csrc/snappy_lane_decode.h $(PKG)/csrc/snappy_pieces.h $(PKG)/csrc/wave_util.h include/flare_snappy_gpu.h include/flare_lz4_gpu.h
 OBJDIR   := build/obj
 
@@ -36,7 +36,14 @@ $(LIB)/libflare_rpc_snappy.so: $(HOST_SRC) $(HOST_HDRS) $(LIB)/libflare_snappy_g
 
 # C++ tests mirroring test/rpc/rpc_snappy_compress_test.cc and the baidu_std /
 # rpc_dump framing (run by pytest)
-cpptests: build/test_rpc_snappy_compress build/test_baidu_std
+cpptests: build/test_rpc_snappy_compress build/test_baidu_std build/test_pack_output
+
+# the handler's packed compress path (outputs packed on the device before the D2H)
+build/test_pack_output: tests/cpp/test_pack_output.cc $(HOST_HDRS) include/flare_snappy_host.h $(LIB)/libflare_rpc_snappy.so $(LIB)/libflare_datagen.so
+	@mkdir -p build
+	$(HOSTCXX) -o $@ $< -I$(PKG)/host -L$(LIB) -lflare_rpc_snappy -lflare_snappy_gpu -lflare_datagen \
+	  -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$(abspath $(LIB)) -Wl,-rpath,'$$ORIGIN/../$(LIB)' \
+	  -Wl,-rpath,/opt/rocm/lib -pthread
 
 build/test_baidu_std: tests/cpp/test_baidu_std.cc $(HOST_HDRS) $(LIB)/libflare_rpc_snappy.so
 	@mkdir -p build
@@ -59,7 +66,13 @@ build/echo_bench: tools/echo_bench.cc $(HOST_HDRS) $(LIB)/libflare_rpc_snappy.so
 	  -Wl,-rpath,/opt/rocm/lib -pthread
 
 # End-to-end rate of the host drop-in path (cord_buf in, cord_buf out)
-hostbench: build/host_bench
+hostbench: build/host_bench build/pack_latency
+# p50 latency of small compress batches with the packed output path on / off
+build/pack_latency: tools/pack_latency.cc $(HOST_HDRS) $(LIB)/libflare_rpc_snappy.so $(LIB)/libflare_datagen.so
+	@mkdir -p build
+	$(HOSTCXX) -o $@ $< -I$(PKG)/host -L$(LIB) -lflare_rpc_snappy -lflare_snappy_gpu -lflare_datagen \
+	  -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$(abspath $(LIB)) -Wl,-rpath,'$$ORIGIN/../$(LIB)' \
+	  -Wl,-rpath,/opt/rocm/lib -pthread
 build/host_bench: tools/host_bench.cc $(HOST_HDRS) $(LIB)/libflare_rpc_snappy.so $(LIB)/libflare_datagen.so
 	@mkdir -p build
 	$(HOSTCXX) -o $@ $< -I$(PKG)/host -L$(LIB) -lflare_rpc_snappy -lflare_snappy_gpu -lflare_datagen \

@@ -40,6 +40,9 @@ hipError_t launch_encode(const u8* in, const u64* in_off, const u32* in_len,
                          u32* out_len, i32* status, hipStream_t stream);
 hipError_t launch_gather_blocks(const u64* src, const u32* len, const u64* dst_off, u32 n, u8* dst,
                                 hipStream_t stream);
+size_t pack_workspace_bytes(u32 n_msgs);
+hipError_t launch_pack(const u8* src, const u64* src_off, const u32* len, const i32* status, u32 n, u32 align,
+                       u8* dst, u64* pack_off, u64* total, void* ws, hipStream_t stream);
 hipError_t launch_decode_partial(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u32 frag,
                                  u8* out, const u64* out_off, const u32* out_cap, u32* got, u64* produced,
                                  i32* status, hipStream_t stream);
@@ -199,6 +202,22 @@ int fsg_gather_blocks(const uint64_t* d_src, const uint32_t* d_len, const uint64
   if (n && (!d_src || !d_len || !d_dst_off || !d_dst)) return FSG_ERR_INVALID_ARG;
   return record(fsg::launch_gather_blocks(d_src, d_len, d_dst_off, n, d_dst, (hipStream_t)stream),
                 "fsg_gather_blocks");
+}
+
+size_t fsg_pack_workspace_bytes(uint32_t n_msgs) { return fsg::pack_workspace_bytes(n_msgs); }
+
+int fsg_pack_batch(const uint8_t* d_src, const uint64_t* d_src_off, const uint32_t* d_len,
+                   const int32_t* d_status, uint32_t n_msgs, uint32_t align, uint8_t* d_dst,
+                   uint64_t* d_pack_off, uint64_t* d_total, void* d_workspace, size_t workspace_bytes,
+                   void* stream) {
+  if (align == 0 || align > 256 || (align & (align - 1)) || !d_total) return FSG_ERR_INVALID_ARG;
+  // offsets and total only (d_dst NULL): the sources are not read
+  if (n_msgs && (!d_len || !d_pack_off || !d_workspace || (d_dst && (!d_src || !d_src_off)) ||
+                 workspace_bytes < fsg::pack_workspace_bytes(n_msgs)))
+    return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_pack(d_src, d_src_off, d_len, d_status, n_msgs, align, d_dst, d_pack_off, d_total,
+                                 d_workspace, (hipStream_t)stream),
+                "fsg_pack_batch");
 }
 
 int fsg_get_uncompressed_length(const void* compressed, size_t n,

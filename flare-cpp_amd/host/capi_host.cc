@@ -22,8 +22,9 @@ void fsh_set_gpu_min_bytes(size_t bytes) { SnappyGpuCodec::Instance().SetMinGpuB
 
 void fsh_stats(uint64_t* out, size_t n) {
   const auto s = SnappyGpuCodec::Instance().stats();
-  const uint64_t v[6] = {s.batches, s.messages, s.cpu_messages, s.fallbacks, s.failures, s.adopted};
-  for (size_t i = 0; i < n && i < 6; ++i) out[i] = v[i];
+  const uint64_t v[8] = {s.batches,  s.messages, s.cpu_messages, s.fallbacks,
+                         s.failures, s.adopted,  s.d2h_bytes,    s.packed_chunks};
+  for (size_t i = 0; i < n && i < 8; ++i) out[i] = v[i];
 }
 
 void fsh_set_park_hooks(const fsh_park_hooks* hooks) {

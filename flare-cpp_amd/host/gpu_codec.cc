@@ -154,7 +154,7 @@ constexpr uint32_t kAdoptMin = 2048;
 
 struct Counters {
   std::atomic<uint64_t> batches{0}, messages{0}, bytes_in{0}, bytes_out{0}, max_batch{0},
-      failures{0}, cpu_messages{0}, fallbacks{0}, adopted{0};
+      failures{0}, cpu_messages{0}, fallbacks{0}, adopted{0}, d2h_bytes{0}, packed_chunks{0};
 };
 
 // One HIP device's runtime.
@@ -167,8 +167,15 @@ struct Device {
   // overrides both (tests force many small chunks).
   size_t chunk_bytes = 256ull << 20;
   size_t chunk_bytes_compress = ~size_t(0);
+  // Compress chunks whose output slots hold at least this many bytes are
+  // packed on the device before the D2H (fsg_pack_batch), so the copy and the
+  // pinned slab carry compressed bytes instead of worst-case slots; smaller
+  // ones take the one-synchronisation path.  FLARE_SNAPPY_GPU_PACK_MIN_BYTES.
+  size_t pack_min_bytes = kPackMinBytesDefault;
   DevBuf d_in, d_meta, d_out, d_ws[kSlots], d_gath;
-  HostBuf h_in, h_meta, h_out, h_gath;
+  // per stream, packed path: the dense outputs; total u64 | pack_off u64[n] | scan workspace
+  DevBuf d_pack[kSlots], d_pmeta[kSlots];
+  HostBuf h_in, h_meta, h_out, h_gath, h_total, h_pack;
 
   bool start(int dev, std::string* err) {
     id = dev;
@@ -187,6 +194,7 @@ struct Device {
       chunk_bytes = std::max<size_t>(1, strtoull(cb, nullptr, 10));
       chunk_bytes_compress = chunk_bytes;
     }
+    pack_min_bytes = PackMinBytesFromEnv();
     return true;
   }
 
@@ -204,6 +212,10 @@ struct Device {
     d_out.release();
     d_gath.release();
     for (auto& w : d_ws) w.release();
+    for (auto& w : d_pack) w.release();
+    for (auto& w : d_pmeta) w.release();
+    h_total.release();
+    h_pack.release();
     h_in.release();
     h_meta.release();
     h_out.release();
@@ -268,13 +280,6 @@ bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
       !d_in.reserve(total_in + 16) || !d_meta.reserve(meta_bytes) || !d_gath.reserve(gath_bytes + 16) ||
       !d_out.reserve(total_out + 16))
     return false;
-  // D2H target: a pinned slab the outputs are adopted from, else staging
-  OutSlab* slab = validate ? nullptr : AcquireOutSlab(total_out + 16);
-  // under slab pressure outputs are copied, so this slab returns to the pool
-  // right after the batch instead of being held by long-lived cord_bufs
-  const bool adopt = slab && !OutSlabsUnderPressure();
-  if (!validate && slab == nullptr && !h_out.reserve(total_out + 16)) return false;
-  uint8_t* hout = slab ? OutSlabData(slab) : h_out.as<uint8_t>();
 
   // Metadata columns, back to back in this order on host and device (the
   // one-chunk path below copies in_off..out_cap and out_len..status as two
@@ -334,10 +339,37 @@ bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
     if (i + 1 < n && in_off[i + 1] - in_off[cut.back()] >= cbytes) cut.push_back(i + 1);
   cut.push_back(n);
   const size_t n_chunks = cut.size() - 1;
+  // ---- which chunks pack their outputs on the device.  The others download
+  // their slot ranges, back to back in chunk order (hbase), into one D2H
+  // target: a pinned slab the outputs are adopted from, else staging.  A
+  // packed chunk gets a slab of its own once its total is known.
+  std::vector<uint8_t> packed(n_chunks, 0);
+  std::vector<size_t> hbase(n_chunks, 0);
+  size_t host_out = 0;
+  bool any_packed = false, any_unpacked = false;
+  for (size_t k = 0; k < n_chunks; ++k) {
+    const size_t oa = out_off[cut[k]], ob = cut[k + 1] < n ? out_off[cut[k + 1]] : pos_out;
+    if (compress && ob > oa && ob - oa >= pack_min_bytes) {
+      packed[k] = 1;
+      any_packed = true;
+    } else {
+      hbase[k] = host_out;
+      host_out += ob - oa;
+      any_unpacked = true;
+    }
+  }
+  if (any_packed && !h_total.reserve(kSlots * sizeof(uint64_t))) return false;
+  OutSlab* slab = validate || !any_unpacked ? nullptr : AcquireOutSlab(host_out + 16);
+  // under slab pressure outputs are copied, so this slab returns to the pool
+  // right after the batch instead of being held by long-lived cord_bufs
+  const bool adopt = slab && !OutSlabsUnderPressure();
+  if (!validate && any_unpacked && slab == nullptr && !h_out.reserve(host_out + 16)) return false;
+  uint8_t* hout = slab ? OutSlabData(slab) : h_out.as<uint8_t>();
 
   bool failed = false;
   std::vector<int> pending(kSlots, -1);  // chunk in flight on each stream
-  uint64_t bytes_in = 0, bytes_out = 0, adopted = 0, corrupt = 0;
+  uint64_t bytes_in = 0, bytes_out = 0, adopted = 0, corrupt = 0, d2h = 0, packed_chunks = 0;
+  std::vector<uint64_t> poff;  // a packed chunk's offsets, by fsg_pack_batch's rule
   auto finish = [&](int slot) {  // wait for a slot's chunk, scatter its results
     const int k = pending[slot];
     if (k < 0) return;
@@ -346,6 +378,40 @@ bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
       fprintf(stderr, "[flare-snappy-gpu] stream error on device %d\n", id);
       failed = true;
       return;
+    }
+    // where message i's bytes are on the host, the slab they are adopted from
+    const uint32_t ka = cut[k];
+    uint8_t* obase = hout + hbase[k];
+    OutSlab* oslab = slab;
+    bool oadopt = adopt;
+    if (packed[k]) {
+      // the lengths and statuses are here: lay the packed outputs out as the
+      // device did, take a slab for exactly that many bytes, download them
+      const uint32_t kb = cut[k + 1];
+      poff.resize(kb - ka);
+      uint64_t tot = 0;
+      for (uint32_t i = ka; i < kb; ++i) {
+        poff[i - ka] = tot;
+        tot += align16(status[i] != FSG_OK ? 0 : out_len[i]);
+      }
+      if (tot != h_total.as<uint64_t>()[slot]) {
+        fprintf(stderr, "[flare-snappy-gpu] packed size mismatch on device %d\n", id);
+        failed = true;
+        return;
+      }
+      oslab = AcquireOutSlab(tot + 16);
+      oadopt = oslab && !OutSlabsUnderPressure();
+      obase = oslab ? OutSlabData(oslab) : (h_pack.reserve(tot + 16) ? h_pack.as<uint8_t>() : nullptr);
+      if (obase == nullptr ||
+          (tot && (hipMemcpyAsync(obase, d_pack[slot].p, tot, hipMemcpyDeviceToHost, streams[slot]) != hipSuccess ||
+                   hipStreamSynchronize(streams[slot]) != hipSuccess))) {
+        fprintf(stderr, "[flare-snappy-gpu] packed D2H failed on device %d\n", id);
+        if (oslab) OutSlabRelease(oslab);
+        failed = true;
+        return;
+      }
+      d2h += tot;
+      ++packed_chunks;
     }
     // ---- scatter: append results to the callers' cord_bufs (serial: page
     // faults from many threads at once measured 3x slower than one thread)
@@ -362,15 +428,17 @@ bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
       bytes_in += in_len[i];
       if (validate) continue;
       const uint32_t L = out_len[i];
-      if (adopt && L >= kAdoptMin) {
-        OutSlabRef(slab);
-        r->out->append_user_data(hout + out_off[i], L, AdoptedDeleter);
+      uint8_t* bytes = obase + (packed[k] ? poff[i - ka] : out_off[i] - out_off[ka]);
+      if (oadopt && L >= kAdoptMin) {
+        OutSlabRef(oslab);
+        r->out->append_user_data(bytes, L, AdoptedDeleter);
         ++adopted;
       } else {
-        r->out->append(hout + out_off[i], L);
+        r->out->append(bytes, L);
       }
       bytes_out += L;
     }
+    if (packed[k] && oslab) OutSlabRelease(oslab);  // the adopted ranges keep it alive
   };
   for (size_t k = 0; k < n_chunks && !failed; ++k) {
     const int slot = (int)(k % kSlots);
@@ -442,6 +510,18 @@ bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
       rc = fsg_compress_batch(d_in.as<uint8_t>(), d_in_off + a, d_in_len + a, cn, cmax,
                               d_out.as<uint8_t>(), d_out_off + a, d_out_len + a, d_status + a, wsp,
                               wsp ? ws : 0, st);
+      if (rc == FSG_SUCCESS && packed[k]) {
+        // dense copies of the outputs, 16-byte aligned (an adopted output that
+        // later feeds a decode keeps fsg_gather_blocks' 16-byte path)
+        const size_t pws = fsg_pack_workspace_bytes(cn);
+        if (d_pack[slot].reserve(ob - oa) && d_pmeta[slot].reserve(8 + 8ull * cn + pws)) {
+          auto* d_total = d_pmeta[slot].as<uint64_t>();
+          rc = fsg_pack_batch(d_out.as<uint8_t>(), d_out_off + a, d_out_len + a, d_status + a, cn, 16,
+                              d_pack[slot].as<uint8_t>(), d_total + 1, d_total, d_total + 1 + cn, pws, st);
+        } else {
+          rc = FSG_ERR_HIP;
+        }
+      }
     } else {
       // two-pass decoder workspace (tag bitmap); without it the single-pass kernel runs
       const size_t ws = validate ? 0 : fsg_decompress_workspace_bytes(cn, ib - ia);
@@ -461,7 +541,11 @@ bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
               : hipMemcpyAsync(out_len + a, d_out_len + a, 4ull * cn, hipMemcpyDeviceToHost, st) == hipSuccess &&
                     hipMemcpyAsync(status + a, d_status + a, 4ull * cn, hipMemcpyDeviceToHost, st) == hipSuccess) &&
          (validate || ob == oa ||
-          hipMemcpyAsync(hout + oa, d_out.as<uint8_t>() + oa, ob - oa, hipMemcpyDeviceToHost, st) == hipSuccess);
+          (packed[k] ? hipMemcpyAsync(h_total.as<uint64_t>() + slot, d_pmeta[slot].p, sizeof(uint64_t),
+                                      hipMemcpyDeviceToHost, st)
+                     : hipMemcpyAsync(hout + hbase[k], d_out.as<uint8_t>() + oa, ob - oa, hipMemcpyDeviceToHost,
+                                      st)) == hipSuccess);
+    if (ok && !validate && !packed[k]) d2h += ob - oa;
     if (!ok) {
       fprintf(stderr, "[flare-snappy-gpu] D2H copy failed on device %d\n", id);
       failed = true;
@@ -484,6 +568,8 @@ bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
   ctr->bytes_out += bytes_out;
   ctr->adopted += adopted;
   ctr->failures += corrupt;
+  ctr->d2h_bytes += d2h;
+  ctr->packed_chunks += packed_chunks;
   uint64_t mb = ctr->max_batch.load();
   while (n > mb && !ctr->max_batch.compare_exchange_weak(mb, n)) {
   }
@@ -806,7 +892,17 @@ CodecStats SnappyGpuCodec::stats() const {
   s.cpu_messages = c.cpu_messages.load();
   s.fallbacks = c.fallbacks.load();
   s.adopted = c.adopted.load();
+  s.d2h_bytes = c.d2h_bytes.load();
+  s.packed_chunks = c.packed_chunks.load();
   return s;
+}
+
+size_t PackMinBytesFromEnv() {
+  const char* e = getenv("FLARE_SNAPPY_GPU_PACK_MIN_BYTES");
+  if (e == nullptr || *e == '\0') return kPackMinBytesDefault;
+  char* end = nullptr;
+  const unsigned long long v = strtoull(e, &end, 10);
+  return end == e ? kPackMinBytesDefault : (size_t)v;  // not a number: the default
 }
 
 void InjectDeviceErrorsForTesting(int n) { g_inject_errors.store(n); }

@@ -42,7 +42,21 @@ struct CodecStats {
   uint64_t cpu_messages = 0;  // messages coded on the host
   uint64_t fallbacks = 0;     // messages moved to the host after a device error
   uint64_t adopted = 0;       // outputs adopted zero-copy from pinned slabs
+  uint64_t d2h_bytes = 0;     // output bytes copied device-to-host (compress and decompress)
+  uint64_t packed_chunks = 0; // compress chunks whose outputs were packed on the device first
 };
+
+// A compress chunk packs its outputs on the device (fsg_pack_batch) before
+// the D2H copy when its output slots hold at least this many bytes: the copy
+// and the pinned slab then carry the compressed bytes (16-byte aligned)
+// instead of the worst-case slots, for one more stream synchronisation.
+// Smaller chunks -- a single small body above all -- keep the
+// one-synchronisation path.  The default is measured ("Packed
+// compress outputs": the threshold table).
+constexpr size_t kPackMinBytesDefault = 2u << 20;
+// FLARE_SNAPPY_GPU_PACK_MIN_BYTES (decimal bytes; 0 = always pack, a huge
+// value = never), else the default.  Read by each device when it starts.
+size_t PackMinBytesFromEnv();
 
 // Park hooks (see fsh_park_hooks in include/flare_snappy_host.h).
 struct ParkHooks {

@@ -35,6 +35,8 @@ _SIGS = {
     "fsg_get_option": (_c.c_int, [_c.c_char_p, _c.POINTER(_c.c_int64)]),
     "fsg_default_option": (_c.c_int, [_c.c_char_p, _c.POINTER(_c.c_int64)]),
     "fsg_max_compressed_length": (_sz, [_sz]),
+    "fsg_pack_workspace_bytes": (_sz, [_u32]),
+    "fsg_pack_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "fsg_get_uncompressed_length": (_c.c_int, [_vp, _sz, _c.POINTER(_u32), _c.c_int]),
     "fsg_uncompressed_lengths_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _c.c_int, _vp]),
     "fsg_compress_workspace_bytes": (_sz, [_u32, _u32]),
@@ -68,7 +70,8 @@ def header_symbols(header: Path | None = None) -> list[str]:
 
 # entry points an older library under A/B may lack
 _OPTIONAL = {"fsg_decompress_batch_2s", "fsg_decompress_batch_partial", "fsg_decompress_batch_iovec", "fsg_lz4_decompress_batch_2s", "fsg_lz4_decompress_batch_ws",
-             "fsg_lz4_decompress_workspace_bytes", "fsg_set_option", "fsg_get_option", "fsg_default_option"}
+             "fsg_lz4_decompress_workspace_bytes", "fsg_set_option", "fsg_get_option", "fsg_default_option",
+             "fsg_pack_workspace_bytes", "fsg_pack_batch"}
 
 
 def load_gpu_lib(path: Path | None = None) -> ctypes.CDLL:
@@ -247,6 +250,23 @@ class SnappyGPU:
             self._check(self.lib.fsg_lz4_decompress_batch_2s(*args, self._stream(pass1_stream)),
                         "fsg_lz4_decompress_batch_2s")
 
+    # ---- pack (fsg_pack_batch)
+    def pack_workspace(self, n, device=None):
+        """Allocate the device workspace fsg_pack_batch wants (torch uint8)."""
+        import torch
+        nbytes = self.lib.fsg_pack_workspace_bytes(n)
+        return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device or f"cuda:{self.device}")
+
+    def pack(self, d_src, d_src_off, d_len, n, d_dst, d_pack_off, d_total, workspace, d_status=None, align=16,
+             stream=None):
+        """fsg_pack_batch: the ranges (d_src + d_src_off[i], d_len[i]) whose status is
+        FSG_OK, dense in d_dst at d_pack_off (int64 / uint64), *d_total bytes in all;
+        d_dst=None computes d_pack_off and d_total only."""
+        self._check(self.lib.fsg_pack_batch(
+            _ptr(d_src), _ptr(d_src_off), _ptr(d_len), _ptr(d_status), n, align, _ptr(d_dst), _ptr(d_pack_off),
+            _ptr(d_total), _ptr(workspace), workspace.numel() * workspace.element_size(),
+            self._stream(stream)), "fsg_pack_batch")
+
     def uncompressed_lengths(self, d_in, d_in_off, d_in_len, n, d_ulen, lenient=True, stream=None):
         self._check(self.lib.fsg_uncompressed_lengths_batch(
             _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_ulen), int(lenient),
@@ -294,6 +314,28 @@ def slot_offsets(caps: np.ndarray, align: int = 16) -> tuple[np.ndarray, int]:
         offs[1:] = np.cumsum(sizes[:-1])
     total = int(sizes.sum()) if len(caps) else 0
     return offs, max(total, align)
+
+
+# fsg_pack_batch's kernels (csrc/pack.hip): items per workgroup of the offset
+# scan, destination bytes per wave of the copy.  The tests place their sizes
+# around these.
+PACK_SCAN_BLOCK = 1024
+PACK_TILE_BYTES = 4096
+
+
+def pack_offsets(lens, status=None, align: int = 16) -> tuple[np.ndarray, int]:
+    """fsg_pack_batch's layout rule on the host: messages whose status is not
+    FSG_OK take no room, the others round_up(len, align) bytes each, in order.
+    Returns the uint64 offsets and the total."""
+    eff = np.asarray(lens).astype(np.uint64)
+    if status is not None:
+        eff = np.where(np.asarray(status) != FSG_OK, np.uint64(0), eff)
+    a = np.uint64(align)
+    sizes = (eff + (a - np.uint64(1))) // a * a
+    ends = np.cumsum(sizes, dtype=np.uint64)
+    offs = np.zeros(len(eff), dtype=np.uint64)
+    offs[1:] = ends[:-1]
+    return offs, int(ends[-1]) if len(eff) else 0
 
 
 def max_compressed_length(n):

@@ -146,6 +146,39 @@ size_t fsg_max_compressed_length(size_t n);
 int fsg_gather_blocks(const uint64_t *d_src, const uint32_t *d_len, const uint64_t *d_dst_off,
                       uint32_t n, uint8_t *d_dst, void *stream);
 
+/* Pack (compaction): makes n byte ranges that lie spread over slots -- the
+ * outputs of fsg_compress_batch or fsg_lz4_compress_batch in their worst-case
+ * slots, or decode outputs -- one dense buffer plus an offsets column, on the
+ * device, so that a D2H copy or a sender moves result bytes only (no
+ * counterpart in the reference, whose Sink appends each message's bytes where
+ * the caller wants them).  With `align` a power of two from 1 to 256:
+ *   eff[i]        = (d_status && d_status[i] != FSG_OK) ? 0 : d_len[i]
+ *   d_pack_off[i] = sum over j < i of round_up(eff[j], align)      (uint64)
+ *   *d_total      = sum over all j of round_up(eff[j], align)
+ *   d_dst[d_pack_off[i] .. + eff[i]) = d_src[d_src_off[i] .. + eff[i])
+ * A message whose status is not FSG_OK takes no room and none of its bytes
+ * are read.  Bytes of d_dst outside those ranges -- alignment padding and
+ * everything from *d_total on -- are NOT written.  d_src and d_dst must not
+ * overlap (not checked).  d_dst = NULL: only the offsets and the total are
+ * computed (d_src / d_src_off may then be NULL too); a caller sizes a
+ * destination that way.  A 16-byte-aligned d_dst with align a multiple of 16
+ * gets aligned 16-byte stores, and such a packed buffer keeps the 16-byte
+ * path of fsg_gather_blocks when it feeds a decode.  Any n_msgs up to
+ * 2^32 - 1, totals in uint64; n_msgs = 0 writes *d_total = 0.  The work is
+ * balanced by destination bytes, not by message, so batches mixing a million
+ * small bodies with bodies of megabytes pack at copy speed.
+ * FSG_ERR_INVALID_ARG, before any HIP call, for a null required pointer
+ * (d_total always; d_len, d_pack_off, d_workspace and, with d_dst, d_src and
+ * d_src_off when n_msgs > 0), an align that is no power of two in 1..256, or
+ * workspace_bytes below fsg_pack_workspace_bytes(n_msgs).  The workspace is
+ * scratch (block sums of the offset scan). */
+size_t fsg_pack_workspace_bytes(uint32_t n_msgs);
+int fsg_pack_batch(const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_len,
+                   const int32_t *d_status /* may be NULL */, uint32_t n_msgs, uint32_t align,
+                   uint8_t *d_dst /* NULL: offsets and total only */, uint64_t *d_pack_off,
+                   uint64_t *d_total /* one u64 */, void *d_workspace, size_t workspace_bytes,
+                   void *stream);
+
 /* Host-side header parse.  lenient != 0: ReadUncompressedLength rules
  * (5th byte's high bits dropped); lenient == 0: Parse32WithLimit rules.
  * Returns the header byte count (1..5), or 0 if the header is invalid. */

@@ -36,8 +36,13 @@ void fsh_set_gpu_min_bytes(size_t bytes);
 
 /* Counters since start: [0] device batches, [1] messages coded on the GPU,
  * [2] messages coded on the host, [3] messages moved to the host after a
- * device error, [4] corrupt-input verdicts, [5] outputs adopted zero-copy.
- * Writes min(n, 6) values. */
+ * device error, [4] corrupt-input verdicts, [5] outputs adopted zero-copy,
+ * [6] output bytes copied device-to-host (compress and decompress; a packed
+ * compress chunk moves its compressed bytes, 16-byte aligned, any other chunk
+ * its whole slot range), [7] compress chunks whose outputs were packed on the
+ * device before that copy (fsg_pack_batch; chunks whose output slots reach
+ * FLARE_SNAPPY_GPU_PACK_MIN_BYTES, 0 = every chunk).
+ * Writes min(n, 8) values; a caller passing 6 sees what it always saw. */
 void fsh_stats(uint64_t* out, size_t n);
 
 /* Park hooks for followers waiting on a coalesced device batch (the

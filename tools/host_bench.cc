@@ -49,6 +49,7 @@ int main(int argc, char** argv) {
   using clk = std::chrono::steady_clock;
   double best_c = 1e30, best_d = 1e30;
   size_t comp_bytes = 0;
+  uint64_t comp_d2h = 0;
   bool ok_all = true;
   for (int r = 0; r < reps; ++r) {
     std::vector<cord_buf> comp(n), back(n);
@@ -60,9 +61,11 @@ int main(int argc, char** argv) {
       ci[i] = &comp[i];
     }
     std::vector<bool> ok;
+    const uint64_t d2h0 = codec.stats().d2h_bytes;
     auto t0 = clk::now();
     codec.CompressBatch(in, co, &ok);
     auto t1 = clk::now();
+    comp_d2h = codec.stats().d2h_bytes - d2h0;  // one compress leg's output D2H
     for (bool b : ok) ok_all = ok_all && b;
     codec.UncompressBatch(ci, bo, &ok);
     auto t2 = clk::now();
@@ -79,12 +82,13 @@ int main(int argc, char** argv) {
   const auto st = codec.stats();
   printf("{\"messages\": %zu, \"size\": %zu, \"ratio\": %.3f, \"compress_gib_s\": %.3f, "
          "\"decompress_gib_s\": %.3f, \"compress_ms\": %.2f, \"decompress_ms\": %.2f, \"round_trip_ok\": %s, "
-         "\"pinned_blocks\": %s, \"adopted\": %llu, \"device_messages\": %llu, "
+         "\"pinned_blocks\": %s, \"adopted\": %llu, \"device_messages\": %llu, \"compress_d2h_bytes\": %llu, "
+         "\"d2h_bytes\": %llu, \"packed_chunks\": %llu, "
          "\"path\": \"cord_buf (8160-B blocks) -> %s -> kernels -> D2H into pinned slabs -> adopted "
          "(append_user_data), chunked over 3 streams\"}\n",
          n, size, raw_bytes / comp_bytes, raw_bytes / best_c / gib, raw_bytes / best_d / gib, best_c * 1e3,
          best_d * 1e3, ok_all ? "true" : "false", pinned ? "true" : "false", (unsigned long long)st.adopted,
-         (unsigned long long)st.messages,
-         pinned ? "GPU gather from pinned blocks" : "memcpy into pinned staging + H2D");
+         (unsigned long long)st.messages, (unsigned long long)comp_d2h, (unsigned long long)st.d2h_bytes,
+         (unsigned long long)st.packed_chunks, pinned ? "GPU gather from pinned blocks" : "memcpy into pinned staging + H2D");
   return ok_all ? 0 : 2;
 }
