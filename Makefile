@@ -36,7 +36,14 @@ $(LIB)/libflare_rpc_snappy.so: $(HOST_SRC) $(HOST_HDRS) $(LIB)/libflare_snappy_g
 
 # C++ tests mirroring test/rpc/rpc_snappy_compress_test.cc and the baidu_std /
 # rpc_dump framing (run by pytest)
-cpptests: build/test_rpc_snappy_compress build/test_baidu_std build/test_pack_output
+cpptests: build/test_rpc_snappy_compress build/test_baidu_std build/test_pack_output build/test_path_report
+
+# the runtime's device-path counters (fsh_device_path_stats)
+build/test_path_report: tests/cpp/test_path_report.cc $(HOST_HDRS) include/flare_snappy_host.h $(LIB)/libflare_rpc_snappy.so $(LIB)/libflare_datagen.so
+	@mkdir -p build
+	$(HOSTCXX) -o $@ $< -I$(PKG)/host -L$(LIB) -lflare_rpc_snappy -lflare_snappy_gpu -lflare_datagen \
+	  -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$(abspath $(LIB)) -Wl,-rpath,'$$ORIGIN/../$(LIB)' \
+	  -Wl,-rpath,/opt/rocm/lib -pthread
 
 # the handler's packed compress path (outputs packed on the device before the D2H)
 build/test_pack_output: tests/cpp/test_pack_output.cc $(HOST_HDRS) include/flare_snappy_host.h $(LIB)/libflare_rpc_snappy.so $(LIB)/libflare_datagen.so

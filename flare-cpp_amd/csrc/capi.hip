@@ -257,6 +257,104 @@ size_t fsg_decompress_workspace_bytes(uint32_t n_msgs, uint64_t total_in_bytes) 
   return total_in_bytes ? fsg::decode_v4_workspace_bytes(n_msgs, total_in_bytes) : 256;
 }
 
+// ---- routing, shared by the batch calls and their path reports
+namespace {
+// fsg_compress_batch: FSG_PATH_MAIN = the lane-per-message encoder with
+// global-memory tables (v3), when the workspace holds them
+int encode_path(bool have_ws, size_t workspace_bytes, size_t need) {
+  const int forced = g_encode_variant.load(std::memory_order_relaxed);
+  if (forced == 1) return FSG_PATH_FORCED;
+  return have_ws && workspace_bytes >= need ? FSG_PATH_MAIN : FSG_PATH_NO_WORKSPACE;
+}
+// decompress_impl: FSG_PATH_MAIN = the two-pass decoder (v4)
+int decode_path(bool have_ws, size_t workspace_bytes, uint32_t n_msgs, uint32_t flags) {
+  const int forced = g_decode_variant.load(std::memory_order_relaxed);
+  if (flags & FSG_FLAG_VALIDATE_ONLY) return FSG_PATH_SINGLE_DESIGN;
+  if (forced == 1 || forced == 3) return FSG_PATH_FORCED;
+  return have_ws && workspace_bytes >= fsg::decode_v4_workspace_bytes(n_msgs, 0) ? FSG_PATH_MAIN
+                                                                                 : FSG_PATH_NO_WORKSPACE;
+}
+bool lz4_two_pass(bool have_ws, size_t workspace_bytes, uint32_t n_msgs) {
+  return have_ws && workspace_bytes >= fsg::lz4_decode_workspace_bytes(n_msgs, 0);
+}
+}  // namespace
+
+size_t fsg_report_header_bytes(void) { return 256; }
+
+int fsg_decompress_report(const void* header_host_copy, uint32_t n_msgs, size_t workspace_bytes, uint32_t flags,
+                          struct fsg_decode_report* out) {
+  if (!out) return FSG_ERR_INVALID_ARG;
+  *out = fsg_decode_report{};
+  out->path = (uint64_t)decode_path(workspace_bytes != 0, workspace_bytes, n_msgs, flags);
+  if (out->path != FSG_PATH_MAIN) {
+    out->single_pass_messages = n_msgs;
+    return FSG_SUCCESS;
+  }
+  out->bitmap_words_capacity = fsg::decode_v4_bitmap_capacity_words(n_msgs, workspace_bytes);
+  if (n_msgs == 0) return FSG_SUCCESS;  // nothing was launched, the header not written
+  if (!header_host_copy) return FSG_ERR_INVALID_ARG;
+  fsg::DecodeHeaderCounts c;
+  fsg::decode_v4_header_counts(header_host_copy, &c);
+  out->fallback_messages = c.fallback;
+  out->fallback_bitmap = c.fallback_bitmap;
+  out->fallback_wide_offsets = c.fallback_wide;
+  out->fallback_pack_guard = c.fallback_guard;
+  out->bitmap_words_requested = c.bitmap_words;
+  out->large_messages = c.large;
+  out->huge_messages = c.huge;
+  return FSG_SUCCESS;
+}
+
+int fsg_compress_report(const void* header_host_copy, uint32_t n_msgs, uint32_t max_in_len, size_t workspace_bytes,
+                        struct fsg_encode_report* out) {
+  if (!out) return FSG_ERR_INVALID_ARG;
+  *out = fsg_encode_report{};
+  const size_t need = fsg::encode_tables_workspace_bytes(n_msgs, max_in_len, nullptr);
+  out->path = (uint64_t)encode_path(workspace_bytes != 0, workspace_bytes, need);
+  if (out->path != FSG_PATH_MAIN) {
+    out->no_workspace_messages = n_msgs;
+    return FSG_SUCCESS;
+  }
+  if (n_msgs == 0) return FSG_SUCCESS;
+  if (!header_host_copy) return FSG_ERR_INVALID_ARG;
+  fsg::EncodeHeaderCounts c;
+  fsg::encode_v3_header_counts(header_host_copy, &c);
+  out->units_listed = c.units;
+  out->split_messages = c.split;
+  out->unit_bytes = c.unit_bytes;
+  out->fallback_messages = c.fallback;
+  // the wave encoder's share: wave_quota, when the wave encoder ran
+  bool planned = false;
+  if (fsg::encode_v3_wave_min(n_msgs, max_in_len, workspace_bytes, need, encode_wave_min(), &planned)) {
+    fsg::u32 share = 0;
+    fsg::u64 all_bytes = 0;
+    fsg::encode_v3_wave_split(&share, &all_bytes);
+    out->wave_units = fsg::wave_quota_of(c.units, c.unit_bytes, share, all_bytes);
+  }
+  return FSG_SUCCESS;
+}
+
+int fsg_lz4_decompress_report(const void* header_host_copy, uint32_t n_msgs, size_t workspace_bytes,
+                              struct fsg_decode_report* out) {
+  if (!out) return FSG_ERR_INVALID_ARG;
+  *out = fsg_decode_report{};
+  if (!lz4_two_pass(workspace_bytes != 0, workspace_bytes, n_msgs)) {
+    out->path = FSG_PATH_SINGLE_DESIGN;
+    out->single_pass_messages = n_msgs;
+    return FSG_SUCCESS;
+  }
+  out->bitmap_words_capacity = fsg::lz4_decode_bitmap_capacity_words(n_msgs, workspace_bytes);
+  if (n_msgs == 0) return FSG_SUCCESS;
+  if (!header_host_copy) return FSG_ERR_INVALID_ARG;
+  fsg::DecodeHeaderCounts c;
+  fsg::lz4_decode_header_counts(header_host_copy, &c);
+  out->fallback_messages = c.fallback;
+  out->fallback_bitmap = c.fallback_bitmap;
+  out->bitmap_words_requested = c.bitmap_words;
+  out->large_messages = c.large;
+  return FSG_SUCCESS;
+}
+
 int fsg_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off,
                        const uint32_t* d_in_len, uint32_t n_msgs,
                        uint32_t max_in_len, uint8_t* d_out,
@@ -269,10 +367,9 @@ int fsg_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off,
   // The lane-per-message encoder with global-memory tables when the
   // workspace allows it (v3: batched speculative probes, the default);
   // otherwise the wave-per-message LDS-table encoder (v1).
-  const int forced = g_encode_variant.load(std::memory_order_relaxed);
   fsg::u32 slots = 0;
   const size_t need = fsg::encode_tables_workspace_bytes(n_msgs, max_in_len, &slots);
-  if ((forced == 0 || forced == 3) && d_workspace && workspace_bytes >= need) {
+  if (encode_path(d_workspace != nullptr, workspace_bytes, need) == FSG_PATH_MAIN) {
     const fsg::u32 cap = max_in_len == 0 || max_in_len > fsg::kBlockSize ? fsg::kBlockSize : max_in_len;
     // Lanes in flight: option encode_lanes caps them; otherwise
     // launch_encode_v3 caps them beside the wave encoder once it knows the
@@ -338,8 +435,8 @@ int decompress_impl(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_
   // tags without touching output for validate-only.  FSG_DECODE_KERNEL or
   // fsg_select_kernels force a variant (A/B runs).
   const int forced = g_decode_variant.load(std::memory_order_relaxed);
-  const bool v4_fits = d_workspace && workspace_bytes >= fsg::decode_v4_workspace_bytes(n_msgs, 0);
-  const bool two_pass = !validate && forced != 1 && forced != 3 && v4_fits;
+  // (decode_path: the same decision, which fsg_decompress_report repeats)
+  const bool two_pass = decode_path(d_workspace != nullptr, workspace_bytes, n_msgs, flags) == FSG_PATH_MAIN;
   if (!two_pass && pass1_stream && pass1_stream != stream) {
     // single-pass kernels run on `stream` alone: order it after pass1_stream,
     // where the caller made the inputs ready
@@ -443,7 +540,7 @@ int fsg_lz4_decompress_batch_ws(const uint8_t* d_in, const uint64_t* d_in_off, c
   if (n_msgs && (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status))
     return FSG_ERR_INVALID_ARG;
   // no usable workspace: the one-pass lane kernel (same results)
-  if (!d_workspace || workspace_bytes < fsg::lz4_decode_workspace_bytes(n_msgs, 0))
+  if (!lz4_two_pass(d_workspace != nullptr, workspace_bytes, n_msgs))
     return fsg_lz4_decompress_batch(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
                                     d_status, stream);
   return record(fsg::launch_lz4_decode2(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
@@ -457,7 +554,7 @@ int fsg_lz4_decompress_batch_2s(const uint8_t* d_in, const uint64_t* d_in_off, c
                                 void* d_workspace, size_t workspace_bytes, void* stream, void* pass1_stream) {
   if (n_msgs && (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status))
     return FSG_ERR_INVALID_ARG;
-  if (!d_workspace || workspace_bytes < fsg::lz4_decode_workspace_bytes(n_msgs, 0)) {
+  if (!lz4_two_pass(d_workspace != nullptr, workspace_bytes, n_msgs)) {
     // the one-pass kernel on `stream`, ordered behind pass1_stream's work
     if (pass1_stream && pass1_stream != stream) {
       hipEvent_t ev = nullptr;

@@ -51,7 +51,7 @@ namespace fsg {
 
 hipError_t launch_lz4_decode_fallback(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                                       const u64* out_off, const u32* out_cap, u32* out_len, i32* status,
-                                      hipStream_t stream);
+                                      u32* fb_count, hipStream_t stream);
 
 namespace {
 
@@ -1147,10 +1147,27 @@ extern "C" int fsg_debug_l4stamps(unsigned long long* out, int reset) {
 // Workspace: [0, 256) counters (0 bitmap words allocated, 1 large blocks
 // listed, 2 large blocks taken) | bm_base[n] | hdr[n] | big_list[n] | bitmap
 // words (round_up(ceil(block / 32), 4) per message <= total / 32 + 4 n).
+// Counter 3: the messages the one-pass lane kernel finished as this launch's
+// fallback (path report, fsg_lz4_decompress_report).
 constexpr u64 kL4Head = 256;
+constexpr u32 kL4CtrFallback = 3;
 __host__ u64 l4_list_bytes(u32 n) { return ((u64)n * 4 + 255) & ~(u64)255; }
 size_t lz4_decode_workspace_bytes(u32 n_msgs, u64 total_in_bytes) {
   return kL4Head + 3 * l4_list_bytes(n_msgs) + 4 * (total_in_bytes / 32 + 4 * (u64)n_msgs + 4);
+}
+// Bitmap capacity in words (whole 16-byte groups) of a workspace of at least
+// lz4_decode_workspace_bytes(n_msgs, 0) bytes; shared by the launch and the
+// path report.
+u64 lz4_decode_bitmap_capacity_words(u32 n_msgs, size_t ws_bytes) {
+  return (ws_bytes - (kL4Head + 3 * l4_list_bytes(n_msgs))) / 16 * 4;
+}
+void lz4_decode_header_counts(const void* header, DecodeHeaderCounts* c) {
+  u32 ctr[kL4CtrFallback + 1];
+  __builtin_memcpy(ctr, header, sizeof(ctr));
+  *c = DecodeHeaderCounts{};
+  c->bitmap_words = ctr[0];
+  c->large = ctr[1];
+  c->fallback = c->fallback_bitmap = ctr[kL4CtrFallback];  // the only cause
 }
 // blocks above this many bytes take the wave walk (FSG_L4_BIG_MIN, read per
 // call: the tests lower it)
@@ -1211,7 +1228,7 @@ hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len
   const i64 bm_opt = opt(kOptLz4BigMin);
   const u32 big_min = bm_opt >= 0 && bm_opt <= 0xffffffffll ? (u32)bm_opt
                                                             : (n_msgs <= kL4SmallBatch ? kL4BigMinSmall : kL4BigMin);
-  const u64 cap_words = (ws_bytes - fixed) / 16 * 4;  // whole 16-byte groups
+  const u64 cap_words = lz4_decode_bitmap_capacity_words(n_msgs, ws_bytes);
   e = hipMemsetAsync(counter, 0, kL4Head, s1);
   if (e != hipSuccess) return e;
   lz4_index_kernel<<<(n_msgs + 63) / 64, 64, 0, s1>>>(in, in_off, in_len, n_msgs, out_cap, out_len, status,
@@ -1232,7 +1249,8 @@ hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len
       in, in_off, in_len, n_msgs, out, out_off, out_len, status, bm_base, hdr, bitmap);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  return launch_lz4_decode_fallback(in, in_off, in_len, n_msgs, out, out_off, out_cap, out_len, status, stream);
+  return launch_lz4_decode_fallback(in, in_off, in_len, n_msgs, out, out_off, out_cap, out_len, status,
+                                    counter + kL4CtrFallback, stream);
 }
 
 }  // namespace fsg

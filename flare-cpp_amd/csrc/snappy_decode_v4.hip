@@ -2218,6 +2218,9 @@ __device__ __forceinline__ void exec5_message(
 #endif
 namespace {
 constexpr u32 kFirstTag = 1u << 23;
+// Path report: the packed pass counts the bodies it hands to pass 3 in the
+// workspace header, at these u32 slots after its batch counter (kWsPackNext).
+constexpr u32 kPackCtrWide = 3, kPackCtrGuard = 4;
 constexpr u32 kMidLit = 896;  // literals up to this length run inside a packed group (56 chunks)
 __device__ __forceinline__ u32 lane_bperm(u32 v, u32 src) {
   return (u32)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v);
@@ -2237,7 +2240,7 @@ __device__ __forceinline__ void exec5_packed(
     const u64* __restrict__ out_off, const u32* __restrict__ out_len, i32* __restrict__ status,
     const u32* __restrict__ bm_base, const u32* __restrict__ bitmap, const u32* __restrict__ perm, u32 first,
     u32 count, u32* ring, const u32* tagtab, u8* sb, const u32x4* sel_tab, const u32x4* mtab, u32 lane,
-    u32 keep_hist) {
+    u32 keep_hist, u32* __restrict__ pack_ctr) {
 #ifdef FSG_STAMPS
   u64 st_[16] = {};
   u64 t_last_ = __builtin_amdgcn_s_memtime();
@@ -2261,6 +2264,9 @@ __device__ __forceinline__ void exec5_packed(
   const bool wide = io + ial + n_in + 64 >= (1ull << 32) || oo + oal + E_m + 64 >= (1ull << 32);
   if (__ballot(ok && wide)) {
     if (ok) status[m] = kNeedFallback;
+    // path report: the bodies this batch hands to pass 3
+    const u64 handed = __ballot(ok);
+    if (lane == 0) atomicAdd(pack_ctr + kPackCtrWide, (u32)__builtin_popcountll(handed));
     return;
   }
   const u32 ioff_m = (u32)io + ial, ooff = (u32)oo + oal;
@@ -2408,6 +2414,7 @@ __device__ __forceinline__ void exec5_packed(
   for (;;) {
     if (++guard > guard_max) {
       if (pk) status[m] = FSG_PACK_GUARD_STATUS;
+      if (lane == 0) atomicAdd(pack_ctr + kPackCtrGuard, np);
       return;
     }
     // ---------- refill the tag ring from the bodies' bitmaps, in order
@@ -2866,7 +2873,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) __attribute__((amdgpu_waves_pe
     const u32 first = bi * batch;
     const u32 cnt = n - first < batch ? n - first : batch;
     exec5_packed(in, in_off, in_len, out, out_off, out_len, status, bm_base, bitmap, walk_perm, lo + first, cnt,
-                 ring, tagtab, sb, sel_tab, mask_tab, lane, keep_hist);
+                 ring, tagtab, sb, sel_tab, mask_tab, lane, keep_hist, batch_next);
   }
 }
 
@@ -2890,11 +2897,25 @@ extern "C" int fsg_debug_stamps(unsigned long long* out, int reset) {
 __global__ __launch_bounds__(64) void fallback_kernel(
     const u8* __restrict__ in, const u64* __restrict__ in_off, const u32* __restrict__ in_len,
     u32 n_msgs, u8* out, const u64* __restrict__ out_off, const u32* __restrict__ out_len,
-    i32* __restrict__ status, u32 flags) {
+    i32* __restrict__ status, u32 flags, const u32* __restrict__ bm_base, u64 bm_capacity_words,
+    u32* __restrict__ fb_count) {
   const u32 m = blockIdx.x * 64 + threadIdx.x;
-  if (m >= n_msgs || status[m] != kNeedFallback) return;
+  const bool mine = m < n_msgs && status[m] == kNeedFallback;
+  // path report: the messages decoded here, and those of them that pass 1
+  // sent (index_prologue's bitmap test, repeated); the packed pass counts its
+  // own.  One ballot per wave, atomics only from a wave that has work.
+  const u64 fb = __ballot(mine);
+  if (!fb) return;
+  const u32 n_in = mine ? in_len[m] : 0u;
+  const u32 bmb = mine ? bm_base[m] : 0u;
+  const u32 words = (((n_in + 31) >> 5) + 3) & ~3u;
+  const u64 fb_bm = __ballot(mine && !(bmb & kSingleLiteral) && (u64)bmb + words > bm_capacity_words);
+  if (threadIdx.x == 0) {
+    atomicAdd(fb_count, (u32)__builtin_popcountll(fb));
+    if (fb_bm) atomicAdd(fb_count + 1, (u32)__builtin_popcountll(fb_bm));
+  }
+  if (!mine) return;
   const u8* ib = in + in_off[m];
-  const u32 n_in = in_len[m];
   u32 ulen = 0;
   const int h = parse_varint_header(ib, n_in, flags & 2u, &ulen);
   status[m] = decode_one(ib + h, ib + n_in, out + out_off[m], out_len[m], true);
@@ -2927,12 +2948,21 @@ constexpr u32 kWsChunkFixNext = 88;
 constexpr u32 kWsChunkCheckNext = 92;
 constexpr u32 kWsChunkFinalNext = 100;
 constexpr u32 kWsPackNext = 104;      // packed execution: batch counter
+// path report (fsg_decompress_report): pass 3's message count, then its
+// causes -- bitmap overflow (counted by pass 3), the packed pass's 32-bit
+// offset check and its iteration guard (counted where the packed pass marks)
+constexpr u32 kWsFallbackCount = 108;
+constexpr u32 kWsFallbackBitmap = 112;
+constexpr u32 kWsFallbackWide = kWsPackNext + 4 * kPackCtrWide;
+constexpr u32 kWsFallbackGuard = kWsPackNext + 4 * kPackCtrGuard;
+static_assert(kWsFallbackBitmap == kWsFallbackCount + 4, "fallback_kernel counts at fb_count[0..1]");
 constexpr u32 kWsCounterBytes = 256;
 // the counters are distinct u32 slots inside the 256-byte header
 constexpr u32 kWsOffsets[] = {kWsBmCounter, kWsSet1BigNext, kWsSet1SegCount, kWsSet1WholeCount, kWsBigCount,
                               kWsHugeCount, kWsSet0BigNext, kWsSet0SegCount, kWsSet0ExecNext, kWsSet0WholeCount,
                               kWsSet1ExecNext, kWsChunkCount, kWsChunkSpecNext, kWsChunkFixNext,
-                              kWsChunkCheckNext, kWsChunkFinalNext, kWsPackNext};
+                              kWsChunkCheckNext, kWsChunkFinalNext, kWsPackNext, kWsFallbackCount,
+                              kWsFallbackBitmap, kWsFallbackWide, kWsFallbackGuard};
 constexpr bool ws_offsets_ok() {
   for (u32 i = 0; i < sizeof(kWsOffsets) / sizeof(kWsOffsets[0]); ++i) {
     if (kWsOffsets[i] % 4 || kWsOffsets[i] + 4 > kWsCounterBytes) return false;
@@ -2952,6 +2982,32 @@ size_t decode_v4_workspace_bytes(u32 n_msgs, u64 total_in_bytes) {
   const u64 words = total_in_bytes / 32 + 4ull * n_msgs + 64;
   const u64 base = 256 + kListBases * base_bytes + 4 * words;
   return (size_t)(base + base / (kChunkRegionDiv - 1) + 512);
+}
+
+// The tag-start bitmap's capacity in words: what the fixed part and the chunk
+// records (at the end, 256-byte aligned whatever ws_bytes: the passes load
+// them with scalar loads, which ignore the low address bits) leave.  Shared by
+// the launch and the path report.  ws_bytes >= decode_v4_workspace_bytes(n, 0).
+u64 decode_v4_bitmap_capacity_words(u32 n_msgs, size_t ws_bytes) {
+  const u64 base_bytes = (4ull * n_msgs + 255) & ~255ull;
+  const u64 chunk_bytes = (ws_bytes / kChunkRegionDiv) & ~255ull;
+  const u64 chunk_off = (ws_bytes - chunk_bytes) & ~255ull;
+  u64 cap_words = (chunk_off - 256 - kListBases * base_bytes) / 4;
+  if (cap_words >= kSingleLiteral) cap_words = kSingleLiteral - 1;  // bases < 2^31 words
+  return cap_words;
+}
+
+void decode_v4_header_counts(const void* header, DecodeHeaderCounts* c) {
+  u32 ctr[kWsCounterBytes / 4];
+  __builtin_memcpy(ctr, header, sizeof(ctr));
+  auto at = [&ctr](u32 off) { return ctr[off / 4]; };
+  c->bitmap_words = at(kWsBmCounter);
+  c->large = at(kWsBigCount);
+  c->huge = at(kWsHugeCount);
+  c->fallback = at(kWsFallbackCount);
+  c->fallback_bitmap = at(kWsFallbackBitmap);
+  c->fallback_wide = at(kWsFallbackWide);
+  c->fallback_guard = at(kWsFallbackGuard);
 }
 
 // Per-device side stream and fork/join events for launch_decode_v4 (created
@@ -3060,13 +3116,11 @@ hipError_t launch_decode_v4(const u8* in, const u64* in_off, const u32* in_len,
   u32* whole_list2 = reinterpret_cast<u32*>(w + 256 + 10 * base_bytes);
   u32* bitmap = reinterpret_cast<u32*>(w + 256 + kListBases * base_bytes);
   // chunk records (chunked pass 1b) at the end, the bitmap before them
-  // (256-byte aligned whatever ws_bytes: the passes load its records with
-  // scalar loads, which ignore the low address bits)
+  // (decode_v4_bitmap_capacity_words)
   const u64 chunk_bytes = (ws_bytes / kChunkRegionDiv) & ~255ull;
   const u64 chunk_off = (ws_bytes - chunk_bytes) & ~255ull;
   u8* const chunk_region = w + chunk_off;
-  u64 cap_words = (chunk_off - 256 - kListBases * base_bytes) / 4;
-  if (cap_words >= kSingleLiteral) cap_words = kSingleLiteral - 1;  // bases < 2^31 words
+  const u64 cap_words = decode_v4_bitmap_capacity_words(n_msgs, ws_bytes);
   // zero the counters and the bitmap (pass 1 writes only groups holding
   // tags) with one fill from the counters to the end of the bitmap: the
   // lists between them are 20 B per message (A/B: C2 0.159 -> 0.157 ms, C3
@@ -3349,7 +3403,8 @@ hipError_t launch_decode_v4(const u8* in, const u64* in_off, const u32* in_len,
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   fallback_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off,
-                                                         out_len, status, flags);
+                                                         out_len, status, flags, bm_base, cap_words,
+                                                         reinterpret_cast<u32*>(w + kWsFallbackCount));
   return hipGetLastError();
 }
 

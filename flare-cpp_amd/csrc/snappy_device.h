@@ -97,13 +97,57 @@ constexpr u32 kWholeUnit = 0x80000000u;  // unit = a whole message (not a fragme
 // wave encoder alone does C3 in ~165 ms, the lanes in ~135 ms, and a sweep
 // of 280 / 400 / 500 / 600 permille measured 97-101 / 94 / 87 / 101 ms).
 // Both kernels compute it from the plan pass's counters.
-__device__ __forceinline__ u32 wave_quota(const u32* ctr, u32 share_permille, u64 all_bytes) {
-  const u32 n_long = ctr[1];
-  const u64 bytes = *reinterpret_cast<const unsigned long long*>(ctr + 6);
+// (wave_quota_of: the formula on plain values, which the path report
+// evaluates on the host from a copy of the counters.)
+__host__ __device__ __forceinline__ u32 wave_quota_of(u32 n_long, u64 bytes, u32 share_permille, u64 all_bytes) {
   if (bytes <= all_bytes) return n_long;
   const u64 q = ((u64)n_long * share_permille + 999) / 1000;
   return q < n_long ? (u32)q : n_long;
 }
+__device__ __forceinline__ u32 wave_quota(const u32* ctr, u32 share_permille, u64 all_bytes) {
+  return wave_quota_of(ctr[1], *reinterpret_cast<const unsigned long long*>(ctr + 6), share_permille, all_bytes);
+}
 
+// Staging regions of a split message (more than one 64 KiB fragment): fragment
+// k is encoded at dst + hdr + k * stride and may fill *room bytes; the gather
+// pass then moves the fragments together.  Every full fragment gets the same
+// stride, 64 bytes short of 64 KiB + 1/6, and the last one the rest of the
+// slot: with f bytes it has at least f + f/6 + 64 * (fragments - 1) + 22 (the
+// encoders keep 48 bytes of spill room), so an incompressible fragment (its
+// bytes + 3) fits whatever the message length.  (An even split of the slot,
+// the earlier rule, left a 70,000-byte body two regions of 40,832 bytes, and
+// every incompressible body whose length is not near a multiple of 64 KiB
+// went to the whole-message fallback.)  region_cap != 0 (test knob) caps
+// every region.  total > kBlockSize.
+__host__ __device__ __forceinline__ u32 split_region(u32 total, u32 hdr, u32 nfr, u32 region_cap, u32 k,
+                                                     u32* room) {
+  const u32 slot = (u32)max_compressed_length(total) - hdr;
+  u32 stride = ((kBlockSize + kBlockSize / 6) & ~15u) - 64;
+  u32 last = slot - (nfr - 1) * stride;
+  if (region_cap && region_cap < stride) stride = region_cap;
+  if (region_cap && region_cap < last) last = region_cap;
+  *room = k == nfr - 1 ? last : stride;
+  return stride;
+}
+
+// ---- path report (capi.hip: fsg_decompress_report and its kin): what each
+// codec's 256-byte workspace header holds after a call, read from a host copy
+struct DecodeHeaderCounts {
+  u32 bitmap_words;  // the bump allocator's final value
+  u32 large, huge;   // messages listed for the wave-per-message index pass
+  u32 fallback, fallback_bitmap, fallback_wide, fallback_guard;  // pass 3 and its causes
+};
+struct EncodeHeaderCounts {
+  u32 units, split, fallback;
+  u64 unit_bytes;
+};
+u64 decode_v4_bitmap_capacity_words(u32 n_msgs, size_t ws_bytes);
+void decode_v4_header_counts(const void* header, DecodeHeaderCounts* c);
+void encode_v3_header_counts(const void* header, EncodeHeaderCounts* c);
+u32 encode_v3_wave_min(u32 n_msgs, u32 max_in_len, size_t ws_bytes, size_t tables_bytes, u32 wave_min,
+                       bool* planned);
+void encode_v3_wave_split(u32* share_permille, u64* all_bytes);
+u64 lz4_decode_bitmap_capacity_words(u32 n_msgs, size_t ws_bytes);
+void lz4_decode_header_counts(const void* header, DecodeHeaderCounts* c);
 
 }  // namespace fsg

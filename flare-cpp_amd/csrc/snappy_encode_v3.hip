@@ -154,10 +154,11 @@ __device__ __forceinline__ u8* emit_literal_global(u8* op, const u8* lit, u32 le
 // item per fragment (fragments compress independently: fresh table, offsets
 // inside the fragment, snappy.cc:875-954), listed by encode_plan_kernel and
 // handed out first; fragment k is staged in region k of the message's slot
-// (R = slot / fragments bytes each) and encode_gather_kernel packs the regions.
+// (split_region, snappy_device.h: one stride for the full fragments, the last
+// one sized by its length) and encode_gather_kernel packs the regions.
 // Then every single-fragment message is one item.  A fragment whose output
-// would not fit its region (only possible for near-incompressible data close
-// to MaxCompressedLength) marks its message kNeedFallback; the fallback pass
+// would not fit its region (only possible for data that expands by close to
+// MaxCompressedLength's 1/6) marks its message kNeedFallback; the fallback pass
 // (FSG_ENC_FALLBACK) re-encodes those messages whole, one lane each.
 constexpr u32 kEncFallback = 1u;
 
@@ -211,11 +212,11 @@ __global__ __launch_bounds__(64) void encode_pipe_kernel(
     u8* region = dst;
     if (staged) {
       const u32 nfr = (total + kBlockSize - 1) >> kBlockLog;
-      u32 R = ((u32)max_compressed_length(total) - hdr) / nfr & ~15u;
-      if (region_cap && region_cap < R) R = region_cap;
+      u32 room_bytes = 0;
+      const u32 R = split_region(total, hdr, nfr, region_cap, f_first >> kBlockLog, &room_bytes);
       region = dst + hdr + (u64)(f_first >> kBlockLog) * R;
       op = region;
-      op_lim = region + R - 32;
+      op_lim = region + room_bytes - 32;
     }
     if (!staged || f_first == 0) {
       u8* h = dst;
@@ -512,6 +513,19 @@ __global__ void encode_plan_kernel(const u32* __restrict__ in_len, u32 n_msgs,
   if (long_min) atomicAdd(reinterpret_cast<unsigned long long*>(ctr + 6), (unsigned long long)len);
 }
 
+// Path report (fsg_compress_report): the split messages handed to the
+// whole-message fallback pass, counted where they are marked.  (ctr[] in use:
+// 0 and 4 the lanes' work counters, 1, 2 and 6..7 above, 5 the wave encoder's.)
+constexpr u32 kEncCtrFallback = 8;
+void encode_v3_header_counts(const void* header, EncodeHeaderCounts* c) {
+  u32 ctr[kEncCtrFallback + 1];
+  __builtin_memcpy(ctr, header, sizeof(ctr));
+  c->units = ctr[1];
+  c->split = ctr[2];
+  c->unit_bytes = ctr[6] | (u64)ctr[7] << 32;
+  c->fallback = ctr[kEncCtrFallback];
+}
+
 // One wave per split message (grid-stride over the list): moves fragments 1..
 // down behind fragment 0
 // (ascending, 4 KiB batches; destinations never pass their sources) and
@@ -530,13 +544,16 @@ __global__ __launch_bounds__(256) void encode_gather_kernel(
     const u32 total = in_len[m];
     const u32 nfr = (total + kBlockSize - 1) >> kBlockLog;
     const u32 hdr = (u32)varint32_len(total);
-    u32 R = ((u32)max_compressed_length(total) - hdr) / nfr & ~15u;
-    if (region_cap && region_cap < R) R = region_cap;
+    u32 room_bytes = 0;
+    const u32 R = split_region(total, hdr, nfr, region_cap, 0u, &room_bytes);
     const u32* sz = sizes + frag_base[m];
     bool bad = false;
     for (u32 k = lane; k < nfr; k += 64) bad = bad || sz[k] == 0xffffffffu;
     if (__any(bad)) {
-      if (lane == 0) status[m] = kNeedFallback;
+      if (lane == 0) {
+        status[m] = kNeedFallback;
+        atomicAdd(&ctr[kEncCtrFallback], 1u);  // path report
+      }
       continue;
     }
     u8* const dst = out + out_off[m];
@@ -617,6 +634,31 @@ size_t encode_plan_bytes(u32 n_msgs, u32 max_in_len) {
   return (size_t)(max_items * 12 + (u64)n_msgs * 8 + 256);
 }
 
+// The wave encoder's lower bound on a unit's bytes for this call (0: the wave
+// encoder does not run), and whether the plan pass runs.  Shared by the
+// launch and the path report.
+u32 encode_v3_wave_min(u32 n_msgs, u32 max_in_len, size_t ws_bytes, size_t tables_bytes, u32 wave_min,
+                       bool* planned) {
+  const size_t plan = encode_plan_bytes(n_msgs, max_in_len);
+  const bool can_split = max_in_len > kBlockSize;
+  if (wave_min && wave_min < kWaveMinBound) wave_min = kWaveMinBound;
+  // A batch of at most one wave of messages (the host runtime's one-caller
+  // batches: the wave encoder's latency for one message is a fraction of one
+  // lane's, 4 KiB text ~0.2 ms against 1.1 ms in the C1 echo trace), or of
+  // short bodies only (kAllWaveMax): every message on the wave encoder
+  if (wave_min && all_on_wave(n_msgs, max_in_len)) wave_min = kInputMarginBytes;
+  if (max_in_len < wave_min) wave_min = 0;  // nothing long enough (or no bound known)
+  *planned = plan && ws_bytes >= tables_bytes + plan && (can_split || wave_min);
+  return *planned ? wave_min : 0u;
+}
+
+// wave_quota's parameters from options encode_wave_share / encode_wave_all_mb
+void encode_v3_wave_split(u32* share_permille, u64* all_bytes) {
+  const i64 share_opt = opt(kOptEncodeWaveShare), all_opt = opt(kOptEncodeWaveAllMb);
+  *share_permille = share_opt >= 0 && share_opt <= 1000 ? (u32)share_opt : 475u;
+  *all_bytes = (all_opt >= 0 && all_opt < (1 << 24) ? (u64)all_opt : 640ull) << 20;
+}
+
 __global__ void encode_wave_kernel(const u8* __restrict__ in, const u64* __restrict__ in_off,
                                    const u32* __restrict__ in_len, u32 n_msgs, u8* out,
                                    const u64* __restrict__ out_off, u32* __restrict__ out_len,
@@ -662,14 +704,9 @@ hipError_t launch_encode_v3(const u8* in, const u64* in_off, const u32* in_len,
   const size_t plan = encode_plan_bytes(n_msgs, max_in_len);
   u32 *items = nullptr, *sizes = nullptr, *frag_base = nullptr, *big_list = nullptr;
   const bool can_split = max_in_len > kBlockSize;
-  if (wave_min && wave_min < kWaveMinBound) wave_min = kWaveMinBound;
-  // A batch of at most one wave of messages (the host runtime's one-caller
-  // batches: the wave encoder's latency for one message is a fraction of one
-  // lane's, 4 KiB text ~0.2 ms against 1.1 ms in the C1 echo trace), or of
-  // short bodies only (kAllWaveMax): every message on the wave encoder
-  if (wave_min && all_on_wave(n_msgs, max_in_len)) wave_min = kInputMarginBytes;
-  if (max_in_len < wave_min) wave_min = 0;  // nothing long enough (or no bound known)
-  if (plan && ws_bytes >= tables_bytes + plan && (can_split || wave_min)) {
+  bool planned = false;
+  wave_min = encode_v3_wave_min(n_msgs, max_in_len, ws_bytes, tables_bytes, wave_min, &planned);
+  if (planned) {
     const u64 max_items = (plan - 256 - (u64)n_msgs * 8) / 12;
     u8* p = reinterpret_cast<u8*>(ws) + tables_bytes;
     items = reinterpret_cast<u32*>(p);
@@ -679,8 +716,6 @@ hipError_t launch_encode_v3(const u8* in, const u64* in_off, const u32* in_len,
     encode_plan_kernel<<<(n_msgs + 255) / 256, 256, 0, stream>>>(in_len, n_msgs, ctr, items, frag_base, big_list,
                                                                  wave_min);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-  } else {
-    wave_min = 0;
   }
   // Lanes in flight beside the wave encoder (decided here, once it is known
   // to run): 3/4 of the messages, at most 131,072.  The lanes' waves share
@@ -700,9 +735,9 @@ hipError_t launch_encode_v3(const u8* in, const u64* in_off, const u32* in_len,
   // units' bytes above the all-on-wave bound, in permille: C3, A/B on one box
   // (profiles/r6/enc/ab_c3_share_sweep*.log), 400 86.3-86.9 ms, 425 80.8-81.0,
   // 450 80.4-80.6, 475 80.2-80.3, 500 82.4-82.6, 550 89.6-90.1.
-  const i64 share_opt = opt(kOptEncodeWaveShare), all_opt = opt(kOptEncodeWaveAllMb);
-  const u32 kShare = share_opt >= 0 && share_opt <= 1000 ? (u32)share_opt : 475u;  // permille
-  const u64 kAllBytes = (all_opt >= 0 && all_opt < (1 << 24) ? (u64)all_opt : 640ull) << 20;
+  u32 kShare = 0;
+  u64 kAllBytes = 0;
+  encode_v3_wave_split(&kShare, &kAllBytes);
   auto pipe = max_in_len > kBlockSize || max_in_len == 0
                   ? encode_pipe_kernel<FSG_V3_PROBES_SPLIT, FSG_V3_POST_PROBES_SPLIT>
                   : encode_pipe_kernel<kKFlat, kPostFlat>;

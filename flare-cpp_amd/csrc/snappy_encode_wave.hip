@@ -755,11 +755,11 @@ __global__ __launch_bounds__(64 * kWaveEncMaxWaves) void encode_wave_kernel(
     u8* region = dst;
     if (staged) {
       const u32 nfr = (total + kBlockSize - 1) >> kBlockLog;
-      u32 R = ((u32)max_compressed_length(total) - hdr) / nfr & ~15u;
-      if (region_cap && region_cap < R) R = region_cap;
+      u32 room_bytes = 0;
+      const u32 R = split_region(total, hdr, nfr, region_cap, f_first >> kBlockLog, &room_bytes);
       region = dst + hdr + (u64)(f_first >> kBlockLog) * R;
       op = region;
-      op_lim = region + R - 32;
+      op_lim = region + room_bytes - 32;
     }
     if (!staged || f_first == 0) {
       if (lane == 0) {

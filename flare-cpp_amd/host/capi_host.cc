@@ -27,6 +27,12 @@ void fsh_stats(uint64_t* out, size_t n) {
   for (size_t i = 0; i < n && i < 8; ++i) out[i] = v[i];
 }
 
+void fsh_device_path_stats(uint64_t* out, size_t n) {
+  const auto s = SnappyGpuCodec::Instance().stats();
+  const uint64_t v[3] = {s.device_fallback_messages, s.device_single_pass_messages, s.device_fallback_batches};
+  for (size_t i = 0; i < n && i < 3; ++i) out[i] = v[i];
+}
+
 void fsh_set_park_hooks(const fsh_park_hooks* hooks) {
   flare::gpu::ParkHooks h;
   if (hooks) {

@@ -154,7 +154,8 @@ constexpr uint32_t kAdoptMin = 2048;
 
 struct Counters {
   std::atomic<uint64_t> batches{0}, messages{0}, bytes_in{0}, bytes_out{0}, max_batch{0},
-      failures{0}, cpu_messages{0}, fallbacks{0}, adopted{0}, d2h_bytes{0}, packed_chunks{0};
+      failures{0}, cpu_messages{0}, fallbacks{0}, adopted{0}, d2h_bytes{0}, packed_chunks{0},
+      device_fallback_messages{0}, device_single_pass_messages{0}, device_fallback_batches{0};
 };
 
 // One HIP device's runtime.
@@ -176,6 +177,8 @@ struct Device {
   // per stream, packed path: the dense outputs; total u64 | pack_off u64[n] | scan workspace
   DevBuf d_pack[kSlots], d_pmeta[kSlots];
   HostBuf h_in, h_meta, h_out, h_gath, h_total, h_pack;
+  // per stream: the workspace's counter header after the batch call (path report)
+  HostBuf h_rep;
 
   bool start(int dev, std::string* err) {
     id = dev;
@@ -216,6 +219,7 @@ struct Device {
     for (auto& w : d_pmeta) w.release();
     h_total.release();
     h_pack.release();
+    h_rep.release();
     h_in.release();
     h_meta.release();
     h_out.release();
@@ -278,7 +282,7 @@ bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
     if (!skip[i]) total_in += align16(reqs[i]->in->size());
   if (!h_in.reserve(total_in + 16) || !h_meta.reserve(meta_bytes) || !h_gath.reserve(gath_bytes + 16) ||
       !d_in.reserve(total_in + 16) || !d_meta.reserve(meta_bytes) || !d_gath.reserve(gath_bytes + 16) ||
-      !d_out.reserve(total_out + 16))
+      !d_out.reserve(total_out + 16) || !h_rep.reserve(kSlots * fsg_report_header_bytes()))
     return false;
 
   // Metadata columns, back to back in this order on host and device (the
@@ -370,6 +374,35 @@ bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
   std::vector<int> pending(kSlots, -1);  // chunk in flight on each stream
   uint64_t bytes_in = 0, bytes_out = 0, adopted = 0, corrupt = 0, d2h = 0, packed_chunks = 0;
   std::vector<uint64_t> poff;  // a packed chunk's offsets, by fsg_pack_batch's rule
+  // Path report: what each slot's batch call was given (its workspace's header
+  // follows the results down on the same stream when it had a workspace)
+  struct CallArgs {
+    uint32_t n = 0, max_len = 0;
+    size_t ws_bytes = 0;  // 0: no workspace
+  } call[kSlots];
+  const size_t rep_bytes = fsg_report_header_bytes();
+  uint64_t fb_messages = 0, fb_batches = 0, single_pass = 0;
+  auto read_report = [&](int slot) {
+    const void* hdr = call[slot].ws_bytes ? h_rep.as<uint8_t>() + rep_bytes * slot : nullptr;
+    uint64_t fb = 0, sp = 0;
+    if (compress) {
+      fsg_encode_report r;
+      if (fsg_compress_report(hdr, call[slot].n, call[slot].max_len, call[slot].ws_bytes, &r) != FSG_SUCCESS) return;
+      fb = r.fallback_messages;
+      sp = r.no_workspace_messages;
+    } else {
+      fsg_decode_report r;
+      if (fsg_decompress_report(hdr, call[slot].n, call[slot].ws_bytes, validate ? FSG_FLAG_VALIDATE_ONLY : 0u,
+                                &r) != FSG_SUCCESS)
+        return;
+      fb = r.fallback_messages;
+      // validate-only is single-pass by design
+      sp = r.path == FSG_PATH_NO_WORKSPACE || r.path == FSG_PATH_FORCED ? r.single_pass_messages : 0;
+    }
+    fb_messages += fb;
+    fb_batches += fb ? 1 : 0;
+    single_pass += sp;
+  };
   auto finish = [&](int slot) {  // wait for a slot's chunk, scatter its results
     const int k = pending[slot];
     if (k < 0) return;
@@ -379,6 +412,7 @@ bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
       failed = true;
       return;
     }
+    read_report(slot);
     // where message i's bytes are on the host, the slab they are adopted from
     const uint32_t ka = cut[k];
     uint8_t* obase = hout + hbase[k];
@@ -510,6 +544,7 @@ bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
       rc = fsg_compress_batch(d_in.as<uint8_t>(), d_in_off + a, d_in_len + a, cn, cmax,
                               d_out.as<uint8_t>(), d_out_off + a, d_out_len + a, d_status + a, wsp,
                               wsp ? ws : 0, st);
+      call[slot] = CallArgs{cn, cmax, wsp ? ws : 0};
       if (rc == FSG_SUCCESS && packed[k]) {
         // dense copies of the outputs, 16-byte aligned (an adopted output that
         // later feeds a decode keeps fsg_gather_blocks' 16-byte path)
@@ -530,7 +565,14 @@ bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
                                 validate ? nullptr : d_out.as<uint8_t>(), validate ? nullptr : d_out_off + a,
                                 validate ? nullptr : d_out_cap + a, d_out_len + a, d_status + a,
                                 validate ? FSG_FLAG_VALIDATE_ONLY : 0u, wsp, wsp ? ws : 0, st);
+      call[slot] = CallArgs{cn, 0, wsp ? ws : 0};
     }
+    // the workspace's counter header, behind the batch's passes on its stream
+    // (a failed reserve() left no workspace: the routing rule alone reports it)
+    if (rc == FSG_SUCCESS && call[slot].ws_bytes >= rep_bytes &&
+        hipMemcpyAsync(h_rep.as<uint8_t>() + rep_bytes * slot, d_ws[slot].p, rep_bytes, hipMemcpyDeviceToHost, st) !=
+            hipSuccess)
+      rc = FSG_ERR_HIP;
     if (rc != FSG_SUCCESS) {
       fprintf(stderr, "[flare-snappy-gpu] batch launch failed on device %d: %s\n", id, fsg_last_error());
       failed = true;
@@ -570,6 +612,9 @@ bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
   ctr->failures += corrupt;
   ctr->d2h_bytes += d2h;
   ctr->packed_chunks += packed_chunks;
+  ctr->device_fallback_messages += fb_messages;
+  ctr->device_single_pass_messages += single_pass;
+  ctr->device_fallback_batches += fb_batches;
   uint64_t mb = ctr->max_batch.load();
   while (n > mb && !ctr->max_batch.compare_exchange_weak(mb, n)) {
   }
@@ -894,6 +939,9 @@ CodecStats SnappyGpuCodec::stats() const {
   s.adopted = c.adopted.load();
   s.d2h_bytes = c.d2h_bytes.load();
   s.packed_chunks = c.packed_chunks.load();
+  s.device_fallback_messages = c.device_fallback_messages.load();
+  s.device_single_pass_messages = c.device_single_pass_messages.load();
+  s.device_fallback_batches = c.device_fallback_batches.load();
   return s;
 }
 

@@ -44,6 +44,12 @@ struct CodecStats {
   uint64_t adopted = 0;       // outputs adopted zero-copy from pinned slabs
   uint64_t d2h_bytes = 0;     // output bytes copied device-to-host (compress and decompress)
   uint64_t packed_chunks = 0; // compress chunks whose outputs were packed on the device first
+  // Which device path the batches took (fsg_decompress_report / fsg_compress_report of
+  // every batch call; bytes and verdicts are the same on every path, the speed is not):
+  uint64_t device_fallback_messages = 0;     // finished by a serial one-lane fallback pass
+  uint64_t device_single_pass_messages = 0;  // run without a usable workspace, or with a forced
+                                             // kernel variant (validate-only does not count)
+  uint64_t device_fallback_batches = 0;      // batch calls with at least one fallback message
 };
 
 // A compress chunk packs its outputs on the device (fsg_pack_batch) before

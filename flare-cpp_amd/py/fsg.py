@@ -25,7 +25,26 @@ FSG_FLAG_VALIDATE_ONLY, FSG_FLAG_STRICT_HEADER = 1, 2
 _c = ctypes
 _vp, _sz, _u32, _u64, _i32 = _c.c_void_p, _c.c_size_t, _c.c_uint32, _c.c_uint64, _c.c_int32
 
+
+
+def _report_struct(name, fields):
+    return type(name, (_c.Structure,), {"_fields_": [(f, _u64) for f in fields]})
+
+
+# struct fsg_decode_report / fsg_encode_report (include/flare_snappy_gpu.h)
+DecodeReport = _report_struct("DecodeReport", (
+    "path", "single_pass_messages", "fallback_messages", "fallback_bitmap", "fallback_wide_offsets",
+    "fallback_pack_guard", "bitmap_words_requested", "bitmap_words_capacity", "large_messages", "huge_messages"))
+EncodeReport = _report_struct("EncodeReport", (
+    "path", "no_workspace_messages", "units_listed", "split_messages", "unit_bytes", "wave_units",
+    "fallback_messages"))
+PATH_MAIN, PATH_SINGLE_DESIGN, PATH_NO_WORKSPACE, PATH_FORCED = 0, 1, 2, 3
+
 _SIGS = {
+    "fsg_report_header_bytes": (_sz, []),
+    "fsg_decompress_report": (_c.c_int, [_vp, _u32, _sz, _u32, _c.POINTER(DecodeReport)]),
+    "fsg_compress_report": (_c.c_int, [_vp, _u32, _u32, _sz, _c.POINTER(EncodeReport)]),
+    "fsg_lz4_decompress_report": (_c.c_int, [_vp, _u32, _sz, _c.POINTER(DecodeReport)]),
     "fsg_version": (_c.c_char_p, []),
     "fsg_init": (_c.c_int, [_c.c_int]),
     "fsg_last_error": (_c.c_char_p, []),
@@ -71,7 +90,8 @@ def header_symbols(header: Path | None = None) -> list[str]:
 # entry points an older library under A/B may lack
 _OPTIONAL = {"fsg_decompress_batch_2s", "fsg_decompress_batch_partial", "fsg_decompress_batch_iovec", "fsg_lz4_decompress_batch_2s", "fsg_lz4_decompress_batch_ws",
              "fsg_lz4_decompress_workspace_bytes", "fsg_set_option", "fsg_get_option", "fsg_default_option",
-             "fsg_pack_workspace_bytes", "fsg_pack_batch"}
+             "fsg_pack_workspace_bytes", "fsg_pack_batch", "fsg_report_header_bytes", "fsg_decompress_report",
+             "fsg_compress_report", "fsg_lz4_decompress_report"}
 
 
 def load_gpu_lib(path: Path | None = None) -> ctypes.CDLL:
@@ -249,6 +269,45 @@ class SnappyGPU:
         else:
             self._check(self.lib.fsg_lz4_decompress_batch_2s(*args, self._stream(pass1_stream)),
                         "fsg_lz4_decompress_batch_2s")
+
+    # ---- path reports (fsg_decompress_report and its kin)
+    def _report_header(self, workspace):
+        """(host copy of the workspace's counter header or None, workspace bytes)
+        -- after a synchronise, so the last call on it has finished."""
+        if workspace is None:
+            return None, 0
+        import torch
+        nbytes = workspace.numel() * workspace.element_size()
+        head = self.lib.fsg_report_header_bytes()
+        if nbytes < head:
+            return None, nbytes  # too short for any workspace path: the routing rule decides
+        torch.cuda.synchronize(workspace.device)
+        host = workspace.view(torch.uint8)[:head].cpu().numpy().tobytes()
+        return _c.create_string_buffer(host, head), nbytes
+
+    @staticmethod
+    def _report_dict(r) -> dict:
+        return {f: int(getattr(r, f)) for f, _ in r._fields_}
+
+    def decompress_report(self, workspace, n, flags=0) -> dict:
+        """fsg_decompress_report of the last decompress call that used
+        `workspace` (None: the call had none), as a dict."""
+        head, nbytes = self._report_header(workspace)
+        r = DecodeReport()
+        self._check(self.lib.fsg_decompress_report(head, n, nbytes, flags, _c.byref(r)), "fsg_decompress_report")
+        return self._report_dict(r)
+
+    def compress_report(self, workspace, n, max_in_len) -> dict:
+        head, nbytes = self._report_header(workspace)
+        r = EncodeReport()
+        self._check(self.lib.fsg_compress_report(head, n, max_in_len, nbytes, _c.byref(r)), "fsg_compress_report")
+        return self._report_dict(r)
+
+    def lz4_decompress_report(self, workspace, n) -> dict:
+        head, nbytes = self._report_header(workspace)
+        r = DecodeReport()
+        self._check(self.lib.fsg_lz4_decompress_report(head, n, nbytes, _c.byref(r)), "fsg_lz4_decompress_report")
+        return self._report_dict(r)
 
     # ---- pack (fsg_pack_batch)
     def pack_workspace(self, n, device=None):

@@ -91,6 +91,16 @@ int fsg_lz4_decompress_batch_2s(const uint8_t *d_in, const uint64_t *d_in_off,
                                 size_t workspace_bytes, void *stream,
                                 void *pass1_stream);
 
+/* Path report of fsg_lz4_decompress_batch_ws / _2s (see "Path reports" in
+ * flare_snappy_gpu.h: a host copy of the workspace's first 256 bytes, the
+ * same limits).  path 0: the two-pass decoder, fallback_messages =
+ * fallback_bitmap = the messages its one-pass kernel finished; path 1: no
+ * usable workspace, every message on the one-pass kernel (by design: it is
+ * what fsg_lz4_decompress_batch runs).  The packed-pass causes and
+ * huge_messages stay 0. */
+int fsg_lz4_decompress_report(const void *header_host_copy, uint32_t n_msgs, size_t workspace_bytes,
+                              struct fsg_decode_report *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -305,6 +305,71 @@ int fsg_decompress_batch_iovec(const uint8_t *d_in, const uint64_t *d_in_off,
                                uint32_t *d_out_len, int32_t *d_status, void *d_workspace,
                                size_t workspace_bytes, void *stream);
 
+/* ---- Path reports: which device path the last batch took.
+ *
+ * Every route yields the same bytes and statuses, but some are far slower: a
+ * serial one-lane-per-message fallback pass finishes the messages the main
+ * passes hand over, and a call without a usable workspace runs wholly on the
+ * single-pass (decode) or wave-per-message (encode) kernels.  The calls count
+ * what they hand over in the first fsg_report_header_bytes (256) bytes of the
+ * workspace; these functions turn a HOST copy of those bytes into counts.
+ *
+ * The library adds no synchronisation: the caller copies the header off the
+ * device itself, on the batch call's stream, next to the status column it
+ * downloads anyway.  The report functions are pure host code: no HIP call, no
+ * device needed.  They repeat the batch call's routing decision from their
+ * arguments (pass the batch call's n_msgs, workspace_bytes, flags and
+ * max_in_len; workspace_bytes = 0 for a NULL workspace) and from the current
+ * fsg_select_kernels / fsg_set_option state, and read the header only when
+ * that routing says the workspace was used; header_host_copy may be NULL
+ * otherwise.
+ *
+ * Two limits.  A report describes the LAST call that used that workspace, so
+ * the header must be copied before the workspace is reused.  And it must be
+ * computed before fsg_select_kernels or the options change, since the routing
+ * is repeated from their current values.
+ *
+ * fsg_decompress_batch_2s takes fsg_decompress_report with its own flags;
+ * fsg_decompress_batch_partial and fsg_decompress_batch_iovec decode through
+ * the same routing with flags = 0, and fsg_decompress_report covers them with
+ * flags = 0.  fsg_lz4_decompress_report (flare_lz4_gpu.h) fills the same
+ * decode struct.
+ *
+ * Return: FSG_SUCCESS, or FSG_ERR_INVALID_ARG when `out` is NULL or when the
+ * header is NULL although the routing says it must be read. */
+enum {
+  FSG_PATH_MAIN = 0,          /* two-pass decoder / table-workspace encoder */
+  FSG_PATH_SINGLE_DESIGN = 1, /* single-pass by design: validate-only, or the LZ4 call without a workspace */
+  FSG_PATH_NO_WORKSPACE = 2,  /* workspace NULL or too small */
+  FSG_PATH_FORCED = 3         /* forced by fsg_select_kernels */
+};
+struct fsg_decode_report {
+  uint64_t path;                   /* FSG_PATH_* */
+  uint64_t single_pass_messages;   /* n_msgs when path != 0 */
+  uint64_t fallback_messages;      /* decoded serially by pass 3; the three causes sum to it */
+  uint64_t fallback_bitmap;        /*   tag bitmap did not fit the workspace */
+  uint64_t fallback_wide_offsets;  /*   packed pass: buffer offsets beyond 32 bits */
+  uint64_t fallback_pack_guard;    /*   packed pass: iteration guard */
+  uint64_t bitmap_words_requested; /* the bitmap allocator's final value */
+  uint64_t bitmap_words_capacity;  /* what workspace_bytes leaves for the bitmap */
+  uint64_t large_messages;         /* indexed by a wave each */
+  uint64_t huge_messages;          /*   the largest of them (listed apart) */
+};
+struct fsg_encode_report {
+  uint64_t path;                  /* 0, 2 or 3 */
+  uint64_t no_workspace_messages; /* n_msgs when path != 0 */
+  uint64_t units_listed;          /* fragments and long messages on the shared list */
+  uint64_t split_messages;        /* messages over 64 KiB */
+  uint64_t unit_bytes;            /* bytes of the listed units */
+  uint64_t wave_units;            /* of units_listed, the wave encoder's share */
+  uint64_t fallback_messages;     /* split messages re-encoded whole by one lane */
+};
+size_t fsg_report_header_bytes(void);
+int fsg_decompress_report(const void *header_host_copy, uint32_t n_msgs, size_t workspace_bytes,
+                          uint32_t flags, struct fsg_decode_report *out);
+int fsg_compress_report(const void *header_host_copy, uint32_t n_msgs, uint32_t max_in_len,
+                        size_t workspace_bytes, struct fsg_encode_report *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,17 @@ void fsh_set_gpu_min_bytes(size_t bytes);
  * Writes min(n, 8) values; a caller passing 6 sees what it always saw. */
 void fsh_stats(uint64_t* out, size_t n);
 
+/* Which device path the batches took, summed since start (the path reports of
+ * include/flare_snappy_gpu.h, read after every batch call from the 256-byte
+ * workspace header that follows the results down): [0] messages finished by
+ * a serial one-lane fallback pass (both codecs), [1] messages of batch calls
+ * that ran without a usable workspace or with a forced kernel variant
+ * (validate-only calls, single-pass by design, do not count), [2] batch calls
+ * with at least one fallback message.  All three stay 0 when every batch
+ * takes the fast path; bytes and verdicts are the same either way.
+ * Writes min(n, 3) values. */
+void fsh_device_path_stats(uint64_t* out, size_t n);
+
 /* Park hooks for followers waiting on a coalesced device batch (the
  * flare::fiber_latch role, /root/reference/flare/fiber/fiber_latch.h:10-28).
  * create() returns a latch, wait() parks until signal(), destroy() frees it.
