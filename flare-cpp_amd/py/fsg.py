@@ -54,6 +54,7 @@ _SIGS = {
     "fsg_get_option": (_c.c_int, [_c.c_char_p, _c.POINTER(_c.c_int64)]),
     "fsg_default_option": (_c.c_int, [_c.c_char_p, _c.POINTER(_c.c_int64)]),
     "fsg_max_compressed_length": (_sz, [_sz]),
+    "fsg_gather_blocks": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp]),
     "fsg_pack_workspace_bytes": (_sz, [_u32]),
     "fsg_pack_batch": (_c.c_int, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "fsg_get_uncompressed_length": (_c.c_int, [_vp, _sz, _c.POINTER(_u32), _c.c_int]),
@@ -325,6 +326,12 @@ class SnappyGPU:
             _ptr(d_src), _ptr(d_src_off), _ptr(d_len), _ptr(d_status), n, align, _ptr(d_dst), _ptr(d_pack_off),
             _ptr(d_total), _ptr(workspace), workspace.numel() * workspace.element_size(),
             self._stream(stream)), "fsg_pack_batch")
+
+    def gather_blocks(self, d_src, d_len, d_dst_off, n, d_dst, stream=None):
+        """fsg_gather_blocks: the n ranges (address d_src[i], d_len[i] bytes) copied to
+        d_dst + d_dst_off[i] (d_src int64 / uint64 device-visible addresses)."""
+        self._check(self.lib.fsg_gather_blocks(_ptr(d_src), _ptr(d_len), _ptr(d_dst_off), n, _ptr(d_dst),
+                                               self._stream(stream)), "fsg_gather_blocks")
 
     def uncompressed_lengths(self, d_in, d_in_off, d_in_len, n, d_ulen, lenient=True, stream=None):
         self._check(self.lib.fsg_uncompressed_lengths_batch(

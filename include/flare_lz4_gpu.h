@@ -14,6 +14,17 @@
  * LZ4 block.  Blocks are byte-equal to LZ4 1.9.x LZ4_compress_default; the
  * decoder accepts exactly the blocks LZ4_decompress_safe(dst capacity =
  * uncompressed length) accepts, except a match of offset 0 (rejected here).
+ *
+ * What the calls write: the contract of flare_snappy_gpu.h ("What a *_batch
+ * call writes") holds here unchanged.  No byte of d_out outside the slots
+ * [d_out_off[i], d_out_off[i] + cap_i) is written, with cap_i = d_out_cap[i]
+ * for the decode calls (0 allowed) and fsg_lz4_max_compressed_length(
+ * d_in_len[i]) for fsg_lz4_compress_batch; slots need no alignment and may
+ * touch.  Inside a slot the bytes at and past d_out_len[i] are unspecified
+ * (the compressor's headroom, a decode slot larger than the body), as is the
+ * whole slot for any status other than FSG_OK.  d_out_len and d_status get
+ * exactly n_msgs entries, nothing is written past workspace_bytes, and the
+ * input arrays are not written.
  */
 #ifndef FLARE_LZ4_GPU_H_
 #define FLARE_LZ4_GPU_H_

@@ -54,6 +54,30 @@
  * On any status other than FSG_OK the content of the output slot is
  * unspecified (the reference's partial output on failure depends on the
  * source fragmentation, snappy.cc:866, and every caller discards it).
+ *
+ * What a *_batch call writes (tests/test_gpu_containment.py holds every
+ * routing to it, byte for byte):
+ *   1. Output slots.  No byte of d_out / d_stage outside the union of the
+ *      slots [off_i, off_i + cap_i) is written, for every message status and
+ *      every routing (kernel variant, option, workspace size, stream form).
+ *      cap_i is d_out_cap[i] / d_stage_cap[i] for the decode calls, and
+ *      fsg_max_compressed_length(d_in_len[i]) (fsg_lz4_max_compressed_length
+ *      for LZ4) for the compress calls.  Slots need no alignment and may
+ *      touch: a neighbour's bytes are never clobbered.  A decode slot may have
+ *      capacity 0.
+ *   2. Slot tails.  Inside a slot, the bytes at and past the reported length
+ *      (d_out_len[i]; d_got[i] for the partial call) are unspecified: the
+ *      encoders use the slot's headroom as spill room for their wide stores,
+ *      a decode slot larger than the body may be written past the body, and
+ *      for any status other than FSG_OK the whole slot is unspecified.
+ *      Callers must not keep data of their own inside a slot.
+ *   3. Validate-only.  With FSG_FLAG_VALIDATE_ONLY nothing in d_out is
+ *      written.
+ *   4. Result columns.  d_out_len, d_status, d_got, d_produced and d_ulen get
+ *      exactly n_msgs entries.
+ *   5. Workspace and input.  Nothing is written past workspace_bytes, and
+ *      d_in, d_in_off, d_in_len, d_out_off and d_out_cap (d_iov_*, d_stage_off
+ *      and d_stage_cap likewise) are not written at all.
  */
 #ifndef FLARE_SNAPPY_GPU_H_
 #define FLARE_SNAPPY_GPU_H_

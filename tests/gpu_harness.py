@@ -3,14 +3,23 @@ bring results back.  torch is used only for device allocations/streams.
 
 Output slots are filled with POISON (0xA5) before every call, never zeros: an
 output byte a kernel fails to write then shows up as 0xA5 instead of passing
-whenever its true value happens to be 0."""
+whenever its true value happens to be 0.
+
+Every call here also runs under the write-containment guards of
+tests/containment.py ("What a *_batch call writes" in
+include/flare_snappy_gpu.h): the slots keep their 16-byte-aligned starts with
+64 poison bytes after each, the result columns carry a sentinel tail, the
+workspace is a view of an allocation 256 bytes longer, and after the call
+every byte outside the slots, the column tails, the bytes past the workspace
+and the input arrays must be as they were."""
 from __future__ import annotations
 
 import numpy as np
 
+import containment as ct
 import fsg
 
-POISON = 0xA5
+POISON = ct.POISON
 
 
 def dev(a: np.ndarray, device="cuda"):
@@ -18,9 +27,61 @@ def dev(a: np.ndarray, device="cuda"):
     return torch.from_numpy(np.ascontiguousarray(a)).to(device)
 
 
-def empty(n: int, dtype, device="cuda"):
+def poisoned(total: int, device="cuda"):
+    """An output buffer of `total` POISON bytes."""
     import torch
-    return torch.empty(max(n, 1), dtype=dtype, device=device)
+    return torch.full((max(int(total), 1),), POISON, dtype=torch.uint8, device=device)
+
+
+def guarded_column(n: int, dtype, fill=None, device="cuda"):
+    """A result column of n entries (`fill`, default the sentinel) followed by
+    ct.COLUMN_TAIL sentinel entries."""
+    import torch
+    col = torch.full((n + ct.COLUMN_TAIL,), ct.SENTINEL, dtype=dtype, device=device)
+    if fill is not None:
+        col[:n] = fill
+    return col
+
+
+def guarded_workspace(nbytes, zero: bool = False, device="cuda"):
+    """(view, whole): a workspace of max(nbytes, 1) bytes as the first bytes
+    of an allocation ct.WORKSPACE_GUARD bytes longer, the surplus POISON.  The
+    call is given the view (the binding passes numel() as workspace_bytes).
+    nbytes None: no workspace."""
+    import torch
+    if nbytes is None:
+        return None, None
+    nbytes = max(int(nbytes), 1)
+    whole = (torch.zeros if zero else torch.empty)(nbytes + ct.WORKSPACE_GUARD, dtype=torch.uint8, device=device)
+    whole[nbytes:] = POISON
+    return whole[:nbytes], whole
+
+
+class Inputs:
+    """Device copies of a call's input arrays, compared with their host
+    originals after the call (item 5 of the contract: never written)."""
+
+    def __init__(self, **arrays):
+        self.host = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+        self.dev = {k: dev(v) for k, v in self.host.items()}
+
+    def __getitem__(self, k):
+        return self.dev[k]
+
+    def check(self):
+        for k, h in self.host.items():
+            ct.check_unwritten(self.dev[k].cpu().numpy(), h, k)
+
+
+def check_call(out, layout, caps, columns, n, whole_ws, inputs, what="d_out"):
+    """After a synchronised call: every byte outside the slots, each column's
+    tail, the bytes past the workspace, the inputs."""
+    ct.check_outside(out, layout, caps, what)
+    for name, col in columns.items():
+        ct.check_column(col.cpu().numpy(), n, name)
+    if whole_ws is not None:
+        ct.check_workspace_guard(whole_ws[-ct.WORKSPACE_GUARD:].cpu().numpy())
+    inputs.check()
 
 
 class GpuCodec:
@@ -34,18 +95,19 @@ class GpuCodec:
         torch = self.torch
         n = len(batch)
         caps = np.array([fsg.max_compressed_length(int(x)) for x in batch.lens], dtype=np.uint64)
-        oo, tot = fsg.slot_offsets(caps)
-        d_in = dev(batch.data)
-        d_io, d_il = dev(batch.offsets), dev(batch.lens)
-        d_out = torch.full((max(tot, 1),), POISON, dtype=torch.uint8, device="cuda")
-        d_oo = dev(oo)
-        d_ol = empty(n, torch.int32)
-        d_st = torch.full((max(n, 1),), -7, dtype=torch.int32, device="cuda")
+        lay = ct.aligned(caps)
+        oo = lay.offs
+        ins = Inputs(d_in=batch.data, d_in_off=batch.offsets, d_in_len=batch.lens, d_out_off=oo)
+        d_out = poisoned(lay.total)
+        d_ol = guarded_column(n, torch.int32)
+        d_st = guarded_column(n, torch.int32, -7)
         mx = int(batch.lens.max()) if n else 0
-        ws = self.codec.compress_workspace(n, mx) if self.use_workspace else None
-        self.codec.compress(d_in, d_io, d_il, n, mx, d_out, d_oo, d_ol, d_st, workspace=ws)
+        ws, whole = guarded_workspace(self.codec.lib.fsg_compress_workspace_bytes(n, mx) if self.use_workspace else None)
+        self.codec.compress(ins["d_in"], ins["d_in_off"], ins["d_in_len"], n, mx, d_out, ins["d_out_off"], d_ol, d_st,
+                            workspace=ws)
         torch.cuda.synchronize()
         out = d_out.cpu().numpy()
+        check_call(out, lay, caps, {"d_out_len": d_ol, "d_status": d_st}, n, whole, ins)
         ol = d_ol.cpu().numpy()[:n].view(np.uint32)
         st = d_st.cpu().numpy()[:n]
         return [out[int(oo[i]):int(oo[i]) + int(ol[i])].tobytes() for i in range(n)], st
@@ -62,20 +124,26 @@ class GpuCodec:
         b = fsg.Batch.from_list(comps)
         n = len(b)
         caps = np.array(caps, dtype=np.uint32)
-        oo, tot = fsg.slot_offsets(caps.astype(np.uint64) + (16 if slot_skew else 0))
-        if slot_skew:
-            oo = oo + (np.arange(n, dtype=np.uint64) * slot_skew) % 16
-        d_out = torch.full((max(tot, 1),), POISON, dtype=torch.uint8, device="cuda")
-        d_ol = empty(n, torch.int32)
-        d_st = torch.full((max(n, 1),), -7, dtype=torch.int32, device="cuda")
+        lay = ct.aligned(caps.astype(np.uint64) + (16 if slot_skew else 0))
+        if slot_skew:  # the 16 spare bytes around a skewed slot are guard too
+            lay = ct.Layout("aligned+skew", lay.offs + (np.arange(n, dtype=np.uint64) * slot_skew) % 16, lay.total)
+        oo = lay.offs
+        ins = Inputs(d_in=b.data, d_in_off=b.offsets, d_in_len=b.lens, d_out_off=oo, d_out_cap=caps)
+        d_out = poisoned(lay.total)
+        d_ol = guarded_column(n, torch.int32)
+        d_st = guarded_column(n, torch.int32, -7)
         total_in = int(b.data.size) if ws_total_in is None else ws_total_in
-        ws = self.codec.decompress_workspace(n, total_in) if self.use_workspace else None
+        ws, whole = guarded_workspace(self.codec.lib.fsg_decompress_workspace_bytes(n, total_in) if self.use_workspace
+                                      else None, zero=True)
         if ws is not None and ws_fill is not None:
             ws.fill_(ws_fill)
-        self.codec.decompress(dev(b.data), dev(b.offsets), dev(b.lens), n, d_out, dev(oo), dev(caps),
-                              d_ol, d_st, flags=flags, workspace=ws)
+        self.codec.decompress(ins["d_in"], ins["d_in_off"], ins["d_in_len"], n, d_out, ins["d_out_off"],
+                              ins["d_out_cap"], d_ol, d_st, flags=flags, workspace=ws)
         torch.cuda.synchronize()
         out = d_out.cpu().numpy()
+        check_call(out, lay, caps, {"d_out_len": d_ol, "d_status": d_st}, n, whole, ins)
+        if flags & fsg.FSG_FLAG_VALIDATE_ONLY:
+            assert (out == POISON).all(), "validate-only call wrote to d_out"
         ol = d_ol.cpu().numpy()[:n].view(np.uint32)
         st = d_st.cpu().numpy()[:n]
         outs = [out[int(oo[i]):int(oo[i]) + int(min(ol[i], caps[i]))].tobytes() for i in range(n)]
@@ -86,15 +154,18 @@ class GpuCodec:
         torch = self.torch
         n = len(batch)
         caps = np.array([self.codec.lib.fsg_lz4_max_compressed_length(int(x)) for x in batch.lens], dtype=np.uint64)
-        oo, tot = fsg.slot_offsets(caps)
-        d_out = torch.full((max(tot, 1),), POISON, dtype=torch.uint8, device="cuda")
-        d_ol = empty(n, torch.int32)
-        d_st = torch.full((max(n, 1),), -7, dtype=torch.int32, device="cuda")
-        ws = self.codec.lz4_compress_workspace(n)
-        self.codec.lz4_compress(dev(batch.data), dev(batch.offsets), dev(batch.lens), n, d_out, dev(oo), d_ol, d_st,
+        lay = ct.aligned(caps)
+        oo = lay.offs
+        ins = Inputs(d_in=batch.data, d_in_off=batch.offsets, d_in_len=batch.lens, d_out_off=oo)
+        d_out = poisoned(lay.total)
+        d_ol = guarded_column(n, torch.int32)
+        d_st = guarded_column(n, torch.int32, -7)
+        ws, whole = guarded_workspace(self.codec.lib.fsg_lz4_compress_workspace_bytes(n))
+        self.codec.lz4_compress(ins["d_in"], ins["d_in_off"], ins["d_in_len"], n, d_out, ins["d_out_off"], d_ol, d_st,
                                 ws)
         torch.cuda.synchronize()
         out = d_out.cpu().numpy()
+        check_call(out, lay, caps, {"d_out_len": d_ol, "d_status": d_st}, n, whole, ins)
         ol = d_ol.cpu().numpy()[:n].view(np.uint32)
         st = d_st.cpu().numpy()[:n]
         return [out[int(oo[i]):int(oo[i]) + int(ol[i])].tobytes() for i in range(n)], st
@@ -108,19 +179,25 @@ class GpuCodec:
         b = fsg.Batch.from_list(bodies)
         n = len(b)
         caps = np.array(caps, dtype=np.uint32)
-        oo, tot = fsg.slot_offsets(caps.astype(np.uint64))
-        d_out = torch.full((max(tot, 1),), POISON, dtype=torch.uint8, device="cuda")
-        d_ol = empty(n, torch.int32)
-        d_st = torch.full((max(n, 1),), -7, dtype=torch.int32, device="cuda")
-        ws = None
+        lay = ct.aligned(caps)
+        oo = lay.offs
+        ins = Inputs(d_in=b.data, d_in_off=b.offsets, d_in_len=b.lens, d_out_off=oo, d_out_cap=caps)
+        d_out = poisoned(lay.total)
+        d_ol = guarded_column(n, torch.int32)
+        d_st = guarded_column(n, torch.int32, -7)
+        ws = whole = None
         if two_pass:
-            ws = self.codec.lz4_decompress_workspace(n, int(b.data.size) if ws_total_in is None else ws_total_in)
-            if ws_fill is not None:
+            lib = self.codec.lib  # (an older library under A/B has no two-pass decoder: the one-pass kernel runs)
+            if hasattr(lib, "fsg_lz4_decompress_workspace_bytes"):
+                ws, whole = guarded_workspace(lib.fsg_lz4_decompress_workspace_bytes(
+                    n, int(b.data.size) if ws_total_in is None else ws_total_in))
+            if ws is not None and ws_fill is not None:
                 ws.fill_(ws_fill)
-        self.codec.lz4_decompress(dev(b.data), dev(b.offsets), dev(b.lens), n, d_out, dev(oo), dev(caps), d_ol, d_st,
-                                  workspace=ws)
+        self.codec.lz4_decompress(ins["d_in"], ins["d_in_off"], ins["d_in_len"], n, d_out, ins["d_out_off"],
+                                  ins["d_out_cap"], d_ol, d_st, workspace=ws)
         torch.cuda.synchronize()
         out = d_out.cpu().numpy()
+        check_call(out, lay, caps, {"d_out_len": d_ol, "d_status": d_st}, n, whole, ins)
         ol = d_ol.cpu().numpy()[:n].view(np.uint32)
         st = d_st.cpu().numpy()[:n]
         outs = [out[int(oo[i]):int(oo[i]) + int(min(ol[i], caps[i]))].tobytes() for i in range(n)]

@@ -10,6 +10,7 @@ import pytest
 import fsg
 from bind import Oracle
 from gen_inputs import build_input
+from snappy_streams import copy_tag as _copy, lit_tag as _lit, synthetic_stream as _synthetic_stream
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 pytestmark = pytest.mark.gpu
@@ -155,8 +156,8 @@ def test_randomized_against_oracle(gpu, oracle, encoder):
     assert (st == 0).all() and all(o == x for o, x in zip(outs, items))
 
 
-@pytest.mark.parametrize("variant,fork", [(0, "0"), (3, "0"), (4, "0"), (0, "1"), (0, "1p"), (0, "1k"), (0, "1s0"),
-                                          (0, "1s1"), (0, "1s2")])
+@pytest.mark.parametrize("variant,fork", [(0, "0"), (3, "0"), (4, "0"), (0, "1"), (0, "1p"), (0, "1k"), (0, "1w"),
+                                          (0, "1s0"), (0, "1s1"), (0, "1s2")])
 def test_decode_fuzz_against_oracle(gpu, oracle, variant, fork, fsg_opts):
     """Mutated and truncated streams (64 B to 70 KB bodies).  fork "1" runs
     the path of batches over 128K messages: plan pass, the large messages'
@@ -165,12 +166,16 @@ def test_decode_fuzz_against_oracle(gpu, oracle, variant, fork, fsg_opts):
     ~150 messages (FSG_SMALL_PERSIST); "1sK" with FSG_SPLIT_WALK=K (0: the
     small bodies executed in message order; 1: walk and execution split by
     size on two streams; 2: one execution launch in walk order; default 3:
-    two execution launches by size); "1k": the smaller bodies packed 32 to a
-    wave (exec_pack 32) instead of one wave each."""
+    two execution launches by size).  The smaller bodies are packed 32 to a
+    wave by default (exec_pack 32), which "1k" sets explicitly, so it runs
+    what "1" runs; "1w" gives them one wave each (exec_pack 0), the small
+    path the packed pass replaced as the default."""
     fsg_opts(decode_fork=fork[0])
     fsg_opts(small_persist="5" if fork == "1p" else "1792")
     if fork == "1k":
         fsg_opts(exec_pack=32)
+    if fork == "1w":
+        fsg_opts(exec_pack=0)
     fsg_opts(split_walk=fork[2] if fork.startswith("1s") else "3")
     gpu.codec.select_kernels(variant, 0)
     rng = np.random.default_rng(9)
@@ -269,55 +274,6 @@ def test_empty_batch_and_empty_messages(gpu):
     assert comps == [b"\x00", b"\x00", b"\x01\x00x"] and (st == 0).all()
     outs, ol, st = gpu.decompress([b"\x00"], [0])
     assert st[0] == 0 and ol[0] == 0
-
-
-def _lit(b: bytes) -> bytes:
-    n = len(b) - 1
-    if n < 60:
-        return bytes([n << 2]) + b
-    k = (n.bit_length() + 7) // 8
-    return bytes([(59 + k) << 2]) + n.to_bytes(k, "little") + b
-
-
-def _copy(off: int, ln: int, wide: bool = False) -> bytes:
-    if wide or off > 0xFFFF:                             # COPY_4
-        return bytes([((ln - 1) << 2) | 3]) + off.to_bytes(4, "little")
-    if 4 <= ln <= 11 and off < 2048:                     # COPY_1
-        return bytes([((off >> 8) << 5) | ((ln - 4) << 2) | 1, off & 0xFF])
-    return bytes([((ln - 1) << 2) | 2]) + off.to_bytes(2, "little")  # COPY_2
-
-
-def _synthetic_stream(rng, target):
-    """A valid-by-construction tag stream stressing what the encoder rarely
-    emits: offsets 1..15 (pattern copies) at every length 1..64, COPY_4,
-    long literals (which jump the decoder's input ring), back-to-back short
-    copies, and output ends at every alignment."""
-    body, out = [], bytearray()
-    first = bytes(rng.integers(0, 256, int(rng.integers(1, 40)), dtype=np.uint8))
-    body.append(_lit(first)); out += first
-    while len(out) < target:
-        r = rng.random()
-        if r < 0.45:
-            off = int(rng.integers(1, min(16, len(out)) + 1))
-        elif r < 0.75:
-            off = int(rng.integers(1, min(300, len(out)) + 1))
-        elif r < 0.85:
-            off = int(rng.integers(1, len(out) + 1))
-        else:
-            n = int(rng.integers(1, 3000 if rng.random() < 0.1 else 30))
-            lit = bytes(rng.integers(0, 256, n, dtype=np.uint8))
-            body.append(_lit(lit)); out += lit
-            continue
-        ln = int(rng.integers(1, 65))
-        body.append(_copy(off, ln, wide=rng.random() < 0.05))
-        for _ in range(ln):
-            out.append(out[-off])
-    hdr = bytearray()
-    n = len(out)
-    while n >= 0x80:
-        hdr.append((n & 0x7F) | 0x80); n >>= 7
-    hdr.append(n)
-    return bytes(hdr) + b"".join(body), bytes(out)
 
 
 @pytest.mark.parametrize("variant", [0, 1, 3, 4])

@@ -19,7 +19,9 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import containment as ct
 import fsg
+import gpu_harness as gh
 from bind import Oracle
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
@@ -40,27 +42,25 @@ def oracle():
     return Oracle()
 
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def _partial(codec, comps, caps, frag):
     """(produced, got bytes per message, status) from the device."""
     import torch
     b = fsg.Batch.from_list(comps)
     n = len(b)
     caps = np.array(caps, dtype=np.uint32)
-    oo, tot = fsg.slot_offsets(caps.astype(np.uint64))
-    d_out = torch.full((max(tot, 1),), POISON, dtype=torch.uint8, device="cuda")
-    d_got = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
-    d_prod = torch.zeros(max(n, 1), dtype=torch.int64, device="cuda")
-    d_st = torch.full((max(n, 1),), -7, dtype=torch.int32, device="cuda")
-    ws = codec.decompress_workspace(n, int(b.data.size))
-    codec.decompress_partial(_dev(b.data), _dev(b.offsets), _dev(b.lens), n, frag, d_out, _dev(oo), _dev(caps),
-                             d_got, d_prod, d_st, workspace=ws)
+    lay = ct.aligned(caps)  # 16-byte-aligned slots, 64 guard bytes after each
+    oo = lay.offs
+    ins = gh.Inputs(d_in=b.data, d_in_off=b.offsets, d_in_len=b.lens, d_out_off=oo, d_out_cap=caps)
+    d_out = gh.poisoned(lay.total)
+    d_got = gh.guarded_column(n, torch.int32, 0)
+    d_prod = gh.guarded_column(n, torch.int64, 0)
+    d_st = gh.guarded_column(n, torch.int32, -7)
+    ws, whole = gh.guarded_workspace(codec.lib.fsg_decompress_workspace_bytes(n, int(b.data.size)), zero=True)
+    codec.decompress_partial(ins["d_in"], ins["d_in_off"], ins["d_in_len"], n, frag, d_out, ins["d_out_off"],
+                             ins["d_out_cap"], d_got, d_prod, d_st, workspace=ws)
     torch.cuda.synchronize()
     out = d_out.cpu().numpy()
+    gh.check_call(out, lay, caps, {"d_got": d_got, "d_produced": d_prod, "d_status": d_st}, n, whole, ins)
     got = d_got.cpu().numpy()[:n].view(np.uint32)
     prod = d_prod.cpu().numpy()[:n]
     st = d_st.cpu().numpy()[:n]
@@ -170,8 +170,8 @@ def _iovec(codec, comps, iov_lens):
     o = Oracle()
     ulens = [u if h else 0 for h, u in (o.header(c) for c in comps)]
     caps = np.array([max(min(u, 1 << 18), 1) for u in ulens], np.uint32)
-    so, stot = fsg.slot_offsets(caps.astype(np.uint64))
-    d_stage = torch.full((max(stot, 1),), POISON, dtype=torch.uint8, device="cuda")
+    lay = ct.aligned(caps)  # the staging slots: 16-byte-aligned, 64 guard bytes after each
+    d_stage = gh.poisoned(lay.total)
     flat = [x for lens in iov_lens for x in lens]
     first = np.zeros(n + 1, np.uint32)
     first[1:] = np.cumsum([len(lens) for lens in iov_lens])
@@ -179,13 +179,17 @@ def _iovec(codec, comps, iov_lens):
     ioff[1:] = np.cumsum(np.array(flat, np.uint64) + 8)  # 8 guard bytes between iovecs
     d_iov = torch.full((int(ioff[-1]) + 1,), POISON, dtype=torch.uint8, device="cuda")
     base = np.array([d_iov.data_ptr() + int(o) for o in ioff[:-1]], np.uint64).view(np.int64)
-    d_ol = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
-    d_st = torch.full((max(n, 1),), -7, dtype=torch.int32, device="cuda")
-    ws = codec.decompress_workspace(n, int(b.data.size))
-    codec.decompress_iovec(_dev(b.data), _dev(b.offsets), _dev(b.lens), n, _dev(base),
-                           _dev(np.array(flat, np.uint64).view(np.int64)), _dev(first), d_stage, _dev(so),
-                           _dev(caps), d_ol, d_st, workspace=ws)
+    ins = gh.Inputs(d_in=b.data, d_in_off=b.offsets, d_in_len=b.lens, d_iov_base=base,
+                    d_iov_len=np.array(flat, np.uint64).view(np.int64), d_iov_first=first, d_stage_off=lay.offs,
+                    d_stage_cap=caps)
+    d_ol = gh.guarded_column(n, torch.int32, 0)
+    d_st = gh.guarded_column(n, torch.int32, -7)
+    ws, whole = gh.guarded_workspace(codec.lib.fsg_decompress_workspace_bytes(n, int(b.data.size)), zero=True)
+    codec.decompress_iovec(ins["d_in"], ins["d_in_off"], ins["d_in_len"], n, ins["d_iov_base"], ins["d_iov_len"],
+                           ins["d_iov_first"], d_stage, ins["d_stage_off"], ins["d_stage_cap"], d_ol, d_st,
+                           workspace=ws)
     torch.cuda.synchronize()
+    gh.check_call(d_stage.cpu().numpy(), lay, caps, {"d_out_len": d_ol, "d_status": d_st}, n, whole, ins, "d_stage")
     mem = d_iov.cpu().numpy()
     st = d_st.cpu().numpy()[:n]
     bufs, k = [], 0
