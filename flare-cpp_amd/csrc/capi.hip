@@ -51,7 +51,8 @@ hipError_t launch_iov_scatter(const u8* in, const u64* in_off, const u32* in_len
                               const u64* iov_len, const u32* iov_first, i32* status, hipStream_t stream);
 size_t lz4_compress_workspace_bytes(u32 n_msgs);
 hipError_t launch_lz4_encode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
-                             const u64* out_off, u32* out_len, i32* status, void* ws, hipStream_t stream);
+                             const u64* out_off, u32* out_len, i32* status, void* ws, size_t ws_bytes, u64 wave_min,
+                             hipStream_t stream);
 hipError_t launch_lz4_decode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                              const u64* out_off, const u32* out_cap, u32* out_len, i32* status,
                              hipStream_t stream);
@@ -97,6 +98,8 @@ constexpr OptDesc kOptDesc[fsg::kOptCount] = {
     {"encode_wave_per_cu", "FSG_ENCODE_WAVE_PER_CU", 0},
     {"encode_wave_wg", "FSG_ENCODE_WAVE_WG", 1},
     {"lz4_big_min", "FSG_L4_BIG_MIN", -1},
+    {"lz4_encode_wave_min", "FSG_L4_ENC_WAVE_MIN", -1},
+    {"lz4_encode_wave_per_cu", "FSG_L4_ENC_WAVE_PER_CU", 0},
 };
 std::atomic<int64_t> g_opt[fsg::kOptCount];
 // the environment, once, when the library is loaded
@@ -277,6 +280,29 @@ int decode_path(bool have_ws, size_t workspace_bytes, uint32_t n_msgs, uint32_t 
 bool lz4_two_pass(bool have_ws, size_t workspace_bytes, uint32_t n_msgs) {
   return have_ws && workspace_bytes >= fsg::lz4_decode_workspace_bytes(n_msgs, 0);
 }
+// fsg_lz4_compress_batch: path 0 = list + lanes + waves (a workspace of
+// fsg_lz4_compress_workspace_bytes), path 1 = the lanes alone on a workspace
+// of the earlier size.  *wave_min: bodies of at least this many bytes take
+// the wave encoder (fsg::kLz4WaveNone: none).
+// Automatic threshold, from the size matrix measured on MI355X (DESIGN.md
+// section 4, profiles/lz4wenc/): in batches of up to 256 bodies the wave
+// encoder was faster in every row, down to the smallest size measured (8 KiB);
+// at 65,536 bodies (C3) the lanes were twice as fast.  Nothing between was
+// measured, so batches over 256 bodies stay on the lanes.
+constexpr uint32_t kLz4WaveBatchMax = 256;
+constexpr fsg::u64 kLz4WaveMinSmallBatch = 8192;
+fsg::u64 lz4_encode_wave_min_auto(uint32_t n_msgs) {
+  return n_msgs <= kLz4WaveBatchMax ? kLz4WaveMinSmallBatch : fsg::kLz4WaveNone;
+}
+int lz4_encode_path(size_t workspace_bytes, uint32_t n_msgs, fsg::u64* wave_min) {
+  if (workspace_bytes < fsg::lz4_compress_workspace_bytes(n_msgs)) {
+    *wave_min = fsg::kLz4WaveNone;
+    return 1;
+  }
+  const int64_t v = fsg::opt(fsg::kOptLz4EncodeWaveMin);
+  *wave_min = v < 0 ? lz4_encode_wave_min_auto(n_msgs) : v >= 0xFFFFFFFFll ? fsg::kLz4WaveNone : (fsg::u64)v;
+  return 0;
+}
 }  // namespace
 
 size_t fsg_report_header_bytes(void) { return 256; }
@@ -352,6 +378,24 @@ int fsg_lz4_decompress_report(const void* header_host_copy, uint32_t n_msgs, siz
   out->fallback_bitmap = c.fallback_bitmap;
   out->bitmap_words_requested = c.bitmap_words;
   out->large_messages = c.large;
+  return FSG_SUCCESS;
+}
+
+int fsg_lz4_compress_report(const void* header_host_copy, uint32_t n_msgs, size_t workspace_bytes,
+                            struct fsg_lz4_encode_report* out) {
+  if (!out) return FSG_ERR_INVALID_ARG;
+  *out = fsg_lz4_encode_report{};
+  fsg::u64 wave_min;
+  out->path = (uint64_t)lz4_encode_path(workspace_bytes, n_msgs, &wave_min);
+  out->wave_min = wave_min < 0xFFFFFFFFull ? wave_min : 0xFFFFFFFFull;
+  out->lane_messages = n_msgs;
+  if (out->path != 0 || n_msgs == 0) return FSG_SUCCESS;
+  if (!header_host_copy) return FSG_ERR_INVALID_ARG;
+  fsg::Lz4EncodeHeaderCounts c;
+  fsg::lz4_encode_header_counts(header_host_copy, &c);
+  out->wave_messages = c.wave_messages;
+  out->wave_bytes = c.wave_bytes;
+  out->lane_messages = n_msgs - c.wave_messages;
   return FSG_SUCCESS;
 }
 
@@ -512,10 +556,12 @@ int fsg_lz4_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off, const 
                            uint32_t n_msgs, uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len,
                            int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream) {
   if (n_msgs && (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len || !d_status ||
-                 !d_workspace || workspace_bytes < fsg::lz4_compress_workspace_bytes(n_msgs)))
+                 !d_workspace || workspace_bytes < fsg::lz4_compress_tables_bytes(n_msgs)))
     return FSG_ERR_INVALID_ARG;
+  fsg::u64 wave_min;  // (the routing of fsg_lz4_compress_report)
+  (void)lz4_encode_path(workspace_bytes, n_msgs, &wave_min);
   return record(fsg::launch_lz4_encode(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_len, d_status,
-                                       d_workspace, (hipStream_t)stream),
+                                       d_workspace, workspace_bytes, wave_min, (hipStream_t)stream),
                 "fsg_lz4_compress_batch");
 }
 

@@ -16,7 +16,8 @@
 // to index ahead (a sequence's length is in its token and extension bytes),
 // so the decode walk is serial per message like Snappy's; the encoder is a
 // serial greedy chain.  Position tables live in the workspace (16 KiB per
-// message), zeroed by the launch.
+// message), zeroed by the launch.  Compress also has a wave per body for the
+// large ones: lz4_encode_wave.hip, which holds the call's routing.
 #include "snappy_device.h"
 
 namespace fsg {
@@ -272,10 +273,11 @@ __host__ __device__ bool lz4_decompress_block(const u8* src, u32 n, u8* dst, u32
 __global__ __launch_bounds__(64) void lz4_encode_kernel(const u8* __restrict__ in, const u64* __restrict__ in_off,
                                                       const u32* __restrict__ in_len, u32 n_msgs, u8* out,
                                                       const u64* __restrict__ out_off, u32* __restrict__ out_len,
-                                                      i32* __restrict__ status, u8* tables) {
+                                                      i32* __restrict__ status, u8* tables, u64 wave_min) {
   const u32 m = blockIdx.x * 64 + threadIdx.x;
   if (m >= n_msgs) return;
   const u32 n = in_len[m];
+  if ((u64)n >= wave_min) return;  // the wave encoder's (lz4_encode_wave.hip)
   u8* ob = out + out_off[m];
   if (n > kLz4MaxInput) {
     out_len[m] = 0;
@@ -337,15 +339,14 @@ __global__ __launch_bounds__(64) void lz4_decode_kernel(const u8* __restrict__ i
 
 }  // namespace
 
-size_t lz4_compress_workspace_bytes(u32 n_msgs) { return (size_t)n_msgs * kLz4TableBytes; }
-
-hipError_t launch_lz4_encode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
-                             const u64* out_off, u32* out_len, i32* status, void* ws, hipStream_t stream) {
+// The lane encoder on the bodies shorter than wave_min; tables: 16 KiB per
+// message, zeroed by the caller (lz4_encode_wave.hip: launch_lz4_encode).
+hipError_t launch_lz4_encode_lanes(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
+                                   const u64* out_off, u32* out_len, i32* status, void* tables, u64 wave_min,
+                                   hipStream_t stream) {
   if (n_msgs == 0) return hipSuccess;
-  hipError_t e = hipMemsetAsync(ws, 0, lz4_compress_workspace_bytes(n_msgs), stream);
-  if (e != hipSuccess) return e;
   lz4_encode_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_len,
-                                                           status, static_cast<u8*>(ws));
+                                                           status, static_cast<u8*>(tables), wave_min);
   return hipGetLastError();
 }
 

@@ -36,6 +36,9 @@ enum Opt : int {
   kOptEncodeWaveWg,       // wave encoder waves per workgroup (1..5; their tables share the workgroup's LDS)
   // LZ4 two-pass decode (lz4_decode2.hip)
   kOptLz4BigMin,          // -1 automatic; blocks above this many bytes take the wave walk
+  // LZ4 compress (lz4_encode_wave.hip)
+  kOptLz4EncodeWaveMin,   // -1 automatic; bodies of at least this many bytes take the wave encoder (>= 0xFFFFFFFF: none)
+  kOptLz4EncodeWavePerCu, // wave encoder waves per CU (0 = as many as LDS holds)
   kOptCount
 };
 

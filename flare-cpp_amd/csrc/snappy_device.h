@@ -149,5 +149,14 @@ u32 encode_v3_wave_min(u32 n_msgs, u32 max_in_len, size_t ws_bytes, size_t table
 void encode_v3_wave_split(u32* share_permille, u64* all_bytes);
 u64 lz4_decode_bitmap_capacity_words(u32 n_msgs, size_t ws_bytes);
 void lz4_decode_header_counts(const void* header, DecodeHeaderCounts* c);
+// LZ4 compress (lz4_encode_wave.hip): bodies of at least wave_min bytes go to
+// the wave encoder; kLz4WaveNone = none do
+constexpr u64 kLz4WaveNone = 1ull << 32;
+struct Lz4EncodeHeaderCounts {
+  u32 listed, wave_messages;
+  u64 wave_bytes;
+};
+size_t lz4_compress_tables_bytes(u32 n_msgs);  // the lanes' tables alone: the workspace before the wave encoder
+void lz4_encode_header_counts(const void* header, Lz4EncodeHeaderCounts* c);
 
 }  // namespace fsg

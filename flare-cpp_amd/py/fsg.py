@@ -38,6 +38,9 @@ DecodeReport = _report_struct("DecodeReport", (
 EncodeReport = _report_struct("EncodeReport", (
     "path", "no_workspace_messages", "units_listed", "split_messages", "unit_bytes", "wave_units",
     "fallback_messages"))
+# struct fsg_lz4_encode_report (include/flare_lz4_gpu.h)
+Lz4EncodeReport = _report_struct("Lz4EncodeReport", (
+    "path", "lane_messages", "wave_messages", "wave_bytes", "wave_min"))
 PATH_MAIN, PATH_SINGLE_DESIGN, PATH_NO_WORKSPACE, PATH_FORCED = 0, 1, 2, 3
 
 _SIGS = {
@@ -45,6 +48,7 @@ _SIGS = {
     "fsg_decompress_report": (_c.c_int, [_vp, _u32, _sz, _u32, _c.POINTER(DecodeReport)]),
     "fsg_compress_report": (_c.c_int, [_vp, _u32, _u32, _sz, _c.POINTER(EncodeReport)]),
     "fsg_lz4_decompress_report": (_c.c_int, [_vp, _u32, _sz, _c.POINTER(DecodeReport)]),
+    "fsg_lz4_compress_report": (_c.c_int, [_vp, _u32, _sz, _c.POINTER(Lz4EncodeReport)]),
     "fsg_version": (_c.c_char_p, []),
     "fsg_init": (_c.c_int, [_c.c_int]),
     "fsg_last_error": (_c.c_char_p, []),
@@ -92,7 +96,7 @@ def header_symbols(header: Path | None = None) -> list[str]:
 _OPTIONAL = {"fsg_decompress_batch_2s", "fsg_decompress_batch_partial", "fsg_decompress_batch_iovec", "fsg_lz4_decompress_batch_2s", "fsg_lz4_decompress_batch_ws",
              "fsg_lz4_decompress_workspace_bytes", "fsg_set_option", "fsg_get_option", "fsg_default_option",
              "fsg_pack_workspace_bytes", "fsg_pack_batch", "fsg_report_header_bytes", "fsg_decompress_report",
-             "fsg_compress_report", "fsg_lz4_decompress_report"}
+             "fsg_compress_report", "fsg_lz4_decompress_report", "fsg_lz4_compress_report"}
 
 
 def load_gpu_lib(path: Path | None = None) -> ctypes.CDLL:
@@ -308,6 +312,14 @@ class SnappyGPU:
         head, nbytes = self._report_header(workspace)
         r = DecodeReport()
         self._check(self.lib.fsg_lz4_decompress_report(head, n, nbytes, _c.byref(r)), "fsg_lz4_decompress_report")
+        return self._report_dict(r)
+
+    def lz4_compress_report(self, workspace, n) -> dict:
+        """fsg_lz4_compress_report of the last fsg_lz4_compress_batch call that
+        used `workspace`: which encoder took how many bodies."""
+        head, nbytes = self._report_header(workspace)
+        r = Lz4EncodeReport()
+        self._check(self.lib.fsg_lz4_compress_report(head, n, nbytes, _c.byref(r)), "fsg_lz4_compress_report")
         return self._report_dict(r)
 
     # ---- pack (fsg_pack_batch)

@@ -41,15 +41,32 @@ extern "C" {
 /* Output slot size of one body: 5 (header) + LZ4_compressBound(n). */
 size_t fsg_lz4_max_compressed_length(size_t n);
 
-/* Device workspace for fsg_lz4_compress_batch: 16 KiB of position table
- * per message. */
+/* Device workspace for fsg_lz4_compress_batch: a 256-byte header, a u32
+ * list of n_msgs entries (rounded up to 256 bytes), then 16 KiB of position
+ * table per message.  The call zeroes what it uses. */
 size_t fsg_lz4_compress_workspace_bytes(uint32_t n_msgs);
 
 /* Batched compress: message i is d_in[d_in_off[i] .. +d_in_len[i]); its body
  * is written to d_out[d_out_off[i] ..] (slot of
  * fsg_lz4_max_compressed_length(d_in_len[i]) bytes, slots disjoint);
  * d_out_len[i] = body length, d_status[i] FSG_OK (FSG_CORRUPT above
- * 0x7E000000 input bytes, LZ4_MAX_INPUT_SIZE). */
+ * 0x7E000000 input bytes, LZ4_MAX_INPUT_SIZE).
+ *
+ * Routing.  Two encoders write the same bytes: one lane per message, and one
+ * wave per message with the position table in LDS (64 probes of the match
+ * search at a time).  A list kernel names the bodies of at least wave_min
+ * bytes; the wave encoder takes those, the lanes the rest, both on `stream`.
+ * wave_min is option lz4_encode_wave_min (FSG_L4_ENC_WAVE_MIN): -1 automatic
+ * (the measured threshold), 0 every body on the waves,
+ * 0xFFFFFFFF or more none.  Option lz4_encode_wave_per_cu
+ * (FSG_L4_ENC_WAVE_PER_CU) caps the wave encoder's resident waves per CU (0:
+ * as many as LDS holds, 16 KiB a wave).
+ *
+ * Workspace rule.  With fsg_lz4_compress_workspace_bytes(n_msgs) bytes or
+ * more the call routes as above.  A workspace of the earlier size, 16 KiB *
+ * n_msgs, is still accepted: the lanes encode every body, with the earlier
+ * layout.  Too small a workspace never changes bytes.  A NULL or smaller
+ * workspace is FSG_ERR_INVALID_ARG. */
 int fsg_lz4_compress_batch(const uint8_t *d_in, const uint64_t *d_in_off,
                            const uint32_t *d_in_len, uint32_t n_msgs,
                            uint8_t *d_out, const uint64_t *d_out_off,
@@ -111,6 +128,24 @@ int fsg_lz4_decompress_batch_2s(const uint8_t *d_in, const uint64_t *d_in_off,
  * huge_messages stay 0. */
 int fsg_lz4_decompress_report(const void *header_host_copy, uint32_t n_msgs, size_t workspace_bytes,
                               struct fsg_decode_report *out);
+
+/* Path report of fsg_lz4_compress_batch ("Path reports" in
+ * flare_snappy_gpu.h: host code without a HIP call, from a host copy of the
+ * workspace's first 256 bytes taken after the call has completed;
+ * header_host_copy may be NULL when path is 1 or n_msgs is 0).  It repeats
+ * the call's routing expression, so it must be asked with the same n_msgs and
+ * workspace_bytes and before the options change.  wave_messages and
+ * wave_bytes are counted on the device by the wave encoder. */
+struct fsg_lz4_encode_report {
+  uint64_t path;           /* 0: list + lanes + waves; 1: old-size workspace, lanes only */
+  uint64_t lane_messages;
+  uint64_t wave_messages;  /* bodies the wave kernel encoded (counted on the device) */
+  uint64_t wave_bytes;     /* their input bytes */
+  uint64_t wave_min;       /* threshold the call used (0xFFFFFFFF: no body on the waves) */
+};
+int fsg_lz4_compress_report(const void *header_host_copy, uint32_t n_msgs,
+                            size_t workspace_bytes,
+                            struct fsg_lz4_encode_report *out);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,15 @@ lines beside it: the oracle (single thread) and the system liblz4 1.9.3 on a
 sample (checkers only, never the product path).
 
     python tools/lz4_bench.py [--n 65536] [--size 65536] [--steps 5]
+
+--matrix: compress alone over the size matrix of the decode wave walk's table
+(DESIGN.md section 4), one JSON line per row: the median, minimum and maximum
+of --launches single launches (HIP events, after two warm-up launches) with
+the wave encoder forced off (lz4_encode_wave_min=0xFFFFFFFF), forced on (0)
+and at the default options.  A library without the option (an earlier build
+under FSG_LIB) gives the default column alone.
+
+    python tools/lz4_bench.py --matrix [--rows 1x8k,c3] [--modes off,on] [--launches 10]
 """
 import argparse
 import json
@@ -22,8 +31,71 @@ import fsg  # noqa: E402
 GIB = float(1 << 30)
 
 
+# name: (bodies, bytes each)
+MATRIX = {"1x8k": (1, 8 << 10), "1x64k": (1, 64 << 10), "64x16k": (64, 16 << 10), "256x64k": (256, 64 << 10),
+          "256x256k": (256, 256 << 10), "1x2m": (1, 2 << 20), "16x4m": (16, 4 << 20), "c3": (65536, 64 << 10)}
+
+
+def matrix(a):
+    import torch
+    dev = torch.device("cuda", 0)
+    codec = fsg.SnappyGPU(0)
+    lib = codec.lib
+    try:
+        fsg.get_option("lz4_encode_wave_min", lib)
+        modes = tuple(m for m in (("off", 0xFFFFFFFF), ("on", 0), ("default", -1)) if m[0] in a.modes.split(","))
+    except KeyError:
+        modes = (("default", None),)
+    H = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    s = torch.cuda.current_stream()
+    for name in (a.rows.split(",") if a.rows else MATRIX):
+        n, size = MATRIX[name]
+        batch = fsg.make_batch(fsg.KIND_TEXT, np.full(n, size, np.uint32))
+        d_raw, d_ro, d_rl = H(batch.data), H(batch.offsets), H(batch.lens)
+        caps = np.array([lib.fsg_lz4_max_compressed_length(int(x)) for x in batch.lens], np.uint64)
+        c_off, c_tot = fsg.slot_offsets(caps)
+        d_co = H(c_off)
+        d_c = torch.zeros(c_tot, dtype=torch.uint8, device=dev)
+        d_cl = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+        ws = codec.lz4_compress_workspace(n)
+        row = {"row": name, "n": n, "size": size, "launches": a.launches}
+        sums = {}
+        for mode, wave_min in modes:
+            if wave_min is not None:
+                fsg.set_option("lz4_encode_wave_min", wave_min, lib)
+            d_c.fill_(0xA5)
+            ms = []
+            for k in range(2 + a.launches):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(s)
+                codec.lz4_compress(d_raw, d_ro, d_rl, n, d_c, d_co, d_cl, d_st, ws, stream=s)
+                e1.record(s)
+                torch.cuda.synchronize()
+                if k >= 2:
+                    ms.append(e0.elapsed_time(e1))
+            lens = d_cl.cpu().numpy().view(np.uint32)
+            sums[mode] = (int(lens.astype(np.uint64).sum()), int((d_st != 0).sum().item()))
+            row[mode] = {"median_ms": round(float(np.median(ms)), 4), "min_ms": round(min(ms), 4),
+                         "max_ms": round(max(ms), 4)}
+            if hasattr(lib, "fsg_lz4_compress_report"):
+                row[mode]["wave_messages"] = codec.lz4_compress_report(ws, n)["wave_messages"]
+        first = next(iter(sums.values()))
+        row["compressed_bytes"] = first[0]
+        row["ok"] = all(v == first and v[1] == 0 for v in sums.values())
+        print(json.dumps(row), flush=True)
+        del d_raw, d_c, ws
+        torch.cuda.empty_cache()
+    if modes[0][1] is not None:
+        fsg.set_option("lz4_encode_wave_min", -1, lib)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--matrix", action="store_true", help="compress over the size matrix, wave encoder off / on / default")
+    ap.add_argument("--rows", default="", help="--matrix: comma-separated rows (default: all of " + ",".join(MATRIX) + ")")
+    ap.add_argument("--modes", default="off,on,default", help="--matrix: which of off,on,default to time")
+    ap.add_argument("--launches", type=int, default=10, help="--matrix: timed launches per row and mode")
     ap.add_argument("--n", type=int, default=65536)
     ap.add_argument("--size", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=5)
@@ -32,6 +104,8 @@ def main():
     ap.add_argument("--no-pipelined", action="store_true",
                     help="skip the stream of two alternating batches (fsg_lz4_decompress_batch_2s)")
     a = ap.parse_args()
+    if a.matrix:
+        return matrix(a)
     import torch
     dev = torch.device("cuda", 0)
     codec = fsg.SnappyGPU(0)

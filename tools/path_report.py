@@ -3,7 +3,8 @@
 does (bodies from the generator, compressed inputs from the GPU encoder in
 their worst-case slots, the decode workspace sized from the slot total), runs
 ONE call at default options and prints its path report
-(fsg_decompress_report / fsg_compress_report, include/flare_snappy_gpu.h) as
+(fsg_decompress_report / fsg_compress_report, include/flare_snappy_gpu.h;
+fsg_lz4_compress_report, include/flare_lz4_gpu.h, for the lz4-* workloads) as
 one JSON line.  The round trip is checked first (zero statuses, decoded bytes
 equal to the raw batch).
 
@@ -27,7 +28,42 @@ WORKLOADS = {
     "cm-decompress": ("decompress", fsg.KIND_MIXED, 1 << 20, None),
     "c3-compress": ("compress", fsg.KIND_TEXT, 65536, 65536),
     "c5-compress": ("compress", fsg.KIND_PROTO, 262144, None),
+    # LZ4 compress: which encoder took the bodies (lanes, or the wave encoder)
+    "lz4-c3-compress": ("lz4-compress", fsg.KIND_TEXT, 65536, 65536),
+    "lz4-256x64k-compress": ("lz4-compress", fsg.KIND_TEXT, 256, 65536),
+    "lz4-16x4m-compress": ("lz4-compress", fsg.KIND_TEXT, 16, 4 << 20),
 }
+
+
+def lz4_compress(args, torch, codec, b, n, H):
+    """One fsg_lz4_compress_batch call, the bodies decoded back, its report."""
+    lib = codec.lib
+    d_raw, d_off, d_len = H(b.data), H(b.offsets), H(b.lens)
+    caps = np.array([lib.fsg_lz4_max_compressed_length(int(x)) for x in b.lens], np.uint64)
+    c_off, c_tot = fsg.slot_offsets(caps)
+    d_c = torch.zeros(c_tot, dtype=torch.uint8, device="cuda")
+    d_coff = H(c_off)
+    d_cl = torch.zeros(n, dtype=torch.int32, device="cuda")
+    d_st = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+    ws = codec.lz4_compress_workspace(n)
+    codec.lz4_compress(d_raw, d_off, d_len, n, d_c, d_coff, d_cl, d_st, ws)
+    rep = codec.lz4_compress_report(ws, n)
+    del ws
+    errors = int((d_st != 0).sum().item())
+    comp_total = int(d_cl.sum(dtype=torch.int64).item())
+    d_out = torch.full((max(b.total, 1),), 0xA5, dtype=torch.uint8, device="cuda")
+    d_ol = torch.zeros(n, dtype=torch.int32, device="cuda")
+    d_st.fill_(-7)
+    codec.lz4_decompress(d_c, d_coff, d_cl, n, d_out, d_off, d_len, d_ol, d_st)
+    torch.cuda.synchronize()
+    errors += int((d_st != 0).sum().item())
+    line = {
+        "workload": args.workload, "n_msgs": n, "raw_bytes": b.total, "compressed_bytes": comp_total,
+        "status_errors": errors, "roundtrip_ok": bool(torch.equal(d_out[:b.total], d_raw[:b.total])),
+        "report": rep,
+    }
+    print(json.dumps(line))
+    return 0 if errors == 0 and line["roundtrip_ok"] else 1
 
 
 def main():
@@ -46,6 +82,8 @@ def main():
         return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
     codec = fsg.SnappyGPU(0)
+    if op == "lz4-compress":
+        return lz4_compress(args, torch, codec, b, n, H)
     d_raw, d_off, d_len = H(b.data), H(b.offsets), H(b.lens)
     caps = np.array([fsg.max_compressed_length(int(x)) for x in b.lens], np.uint64)
     c_off, c_tot = fsg.slot_offsets(caps)
