@@ -8,59 +8,10 @@
 
 #include "../../include/flare_lz4_gpu.h"
 #include "../../include/flare_snappy_gpu.h"
+#include "launch.h"
+#include "launch_util.h"
 #include "options.h"
 #include "snappy_device.h"
-
-namespace fsg {
-hipError_t launch_decode(const u8* in, const u64* in_off, const u32* in_len,
-                         u32 n_msgs, u8* out, const u64* out_off,
-                         const u32* out_cap, u32* out_len, i32* status,
-                         u32 flags, hipStream_t stream);
-hipError_t launch_decode_v3(const u8* in, const u64* in_off, const u32* in_len,
-                            u32 n_msgs, u8* out, const u64* out_off,
-                            const u32* out_cap, u32* out_len, i32* status,
-                            u32 flags, hipStream_t stream);
-size_t decode_v4_workspace_bytes(u32 n_msgs, u64 total_in_bytes);
-hipError_t launch_decode_v4(const u8* in, const u64* in_off, const u32* in_len,
-                            u32 n_msgs, u8* out, const u64* out_off,
-                            const u32* out_cap, u32* out_len, i32* status,
-                            u32 flags, void* ws, size_t ws_bytes, hipStream_t stream,
-                            int exec_variant, hipStream_t pass1_stream);
-hipError_t launch_headers(const u8* in, const u64* in_off, const u32* in_len,
-                          u32 n_msgs, u32* ulen, int lenient, hipStream_t stream);
-size_t encode_tables_workspace_bytes(u32 n_msgs, u32 max_in_len, u32* slots_out);
-size_t encode_plan_bytes(u32 n_msgs, u32 max_in_len);
-hipError_t launch_encode_v3(const u8* in, const u64* in_off, const u32* in_len,
-                            u32 n_msgs, u32 max_in_len, u8* out, const u64* out_off,
-                            u32* out_len, i32* status, void* ws, size_t ws_bytes,
-                            u32 slots, u32 entries, size_t tables_bytes, u32 region_cap,
-                            hipStream_t stream, u32 wave_min);
-hipError_t launch_encode(const u8* in, const u64* in_off, const u32* in_len,
-                         u32 n_msgs, u32 max_in_len, u8* out, const u64* out_off,
-                         u32* out_len, i32* status, hipStream_t stream);
-hipError_t launch_gather_blocks(const u64* src, const u32* len, const u64* dst_off, u32 n, u8* dst,
-                                hipStream_t stream);
-size_t pack_workspace_bytes(u32 n_msgs);
-hipError_t launch_pack(const u8* src, const u64* src_off, const u32* len, const i32* status, u32 n, u32 align,
-                       u8* dst, u64* pack_off, u64* total, void* ws, hipStream_t stream);
-hipError_t launch_decode_partial(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u32 frag,
-                                 u8* out, const u64* out_off, const u32* out_cap, u32* got, u64* produced,
-                                 i32* status, hipStream_t stream);
-hipError_t launch_iov_scatter(const u8* in, const u64* in_off, const u32* in_len, const u8* stage,
-                              const u64* stage_off, const u32* out_len, u32 n_msgs, const u64* iov_base,
-                              const u64* iov_len, const u32* iov_first, i32* status, hipStream_t stream);
-size_t lz4_compress_workspace_bytes(u32 n_msgs);
-hipError_t launch_lz4_encode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
-                             const u64* out_off, u32* out_len, i32* status, void* ws, size_t ws_bytes, u64 wave_min,
-                             hipStream_t stream);
-hipError_t launch_lz4_decode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
-                             const u64* out_off, const u32* out_cap, u32* out_len, i32* status,
-                             hipStream_t stream);
-size_t lz4_decode_workspace_bytes(u32 n_msgs, u64 total_in_bytes);
-hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
-                              const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
-                              size_t ws_bytes, hipStream_t stream, hipStream_t pass1_stream);
-}  // namespace fsg
 
 namespace {
 thread_local char g_err[256] = "";
@@ -101,6 +52,18 @@ constexpr OptDesc kOptDesc[fsg::kOptCount] = {
     {"lz4_encode_wave_min", "FSG_L4_ENC_WAVE_MIN", -1},
     {"lz4_encode_wave_per_cu", "FSG_L4_ENC_WAVE_PER_CU", 0},
 };
+// DecodeOpts' initialisers (decode_v4_plan.h, which the CPU test of the launch
+// plan uses as "the defaults") are this table's
+constexpr bool decode_opts_defaults_ok() {
+  constexpr fsg::DecodeOpts o;
+  const int64_t v[] = {o.decode_fork, o.split_walk, o.split_class, o.exec_keep, o.chunked_huge,
+                       o.small_persist, o.small_batch, o.split_huge, o.walk_order, o.lean_walk,
+                       o.exec_big_blocks, o.exec_prio, o.exec_big_blocks_fork, o.exec_pack};
+  for (int i = 0; i <= fsg::kOptExecPack; ++i)
+    if (v[i] != kOptDesc[i].dflt) return false;
+  return true;
+}
+static_assert(fsg::kOptExecPack == 13 && decode_opts_defaults_ok(), "DecodeOpts defaults differ from the option table");
 std::atomic<int64_t> g_opt[fsg::kOptCount];
 // the environment, once, when the library is loaded
 [[maybe_unused]] const bool g_opt_init = [] {
@@ -484,11 +447,7 @@ int decompress_impl(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_
   if (!two_pass && pass1_stream && pass1_stream != stream) {
     // single-pass kernels run on `stream` alone: order it after pass1_stream,
     // where the caller made the inputs ready
-    hipEvent_t ev = nullptr;
-    hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(ev, (hipStream_t)pass1_stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent((hipStream_t)stream, ev, 0);
-    if (ev) (void)hipEventDestroy(ev);
+    const hipError_t e = fsg::order_after((hipStream_t)stream, (hipStream_t)pass1_stream);
     if (e != hipSuccess) return record(e, "fsg_decompress_batch_2s");
   }
   if (validate || forced == 1)
@@ -603,11 +562,7 @@ int fsg_lz4_decompress_batch_2s(const uint8_t* d_in, const uint64_t* d_in_off, c
   if (!lz4_two_pass(d_workspace != nullptr, workspace_bytes, n_msgs)) {
     // the one-pass kernel on `stream`, ordered behind pass1_stream's work
     if (pass1_stream && pass1_stream != stream) {
-      hipEvent_t ev = nullptr;
-      hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventRecord(ev, (hipStream_t)pass1_stream);
-      if (e == hipSuccess) e = hipStreamWaitEvent((hipStream_t)stream, ev, 0);
-      if (ev) (void)hipEventDestroy(ev);
+      const hipError_t e = fsg::order_after((hipStream_t)stream, (hipStream_t)pass1_stream);
       if (e != hipSuccess) return record(e, "fsg_lz4_decompress_batch_2s");
     }
     return fsg_lz4_decompress_batch(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,

@@ -4,6 +4,7 @@
 // host runtime needs neither a staging memcpy nor one hipMemcpyAsync per
 // 8 KiB block (cord_buf.cc:1469-1475 is the reference's per-block walk).
 #include "../../include/flare_snappy_gpu.h"
+#include "launch.h"
 #include "snappy_device.h"
 
 namespace fsg {

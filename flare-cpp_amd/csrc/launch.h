@@ -1,0 +1,102 @@
+// launch.h -- the host entry points of the codec kernels: every launch_*,
+// *_workspace_bytes and path-report function, declared once.  Included by
+// capi.hip (the callers) and by each .hip that defines one, so a definition
+// that drifts from its declaration no longer links as an overload nobody
+// calls.
+#pragma once
+
+#include "decode_v4_plan.h"  // decode_v4_workspace_bytes, decode_v4_bitmap_capacity_words (inline)
+#include "snappy_device.h"
+
+namespace fsg {
+
+// ---- Snappy decode
+hipError_t launch_decode(const u8* in, const u64* in_off, const u32* in_len,
+                         u32 n_msgs, u8* out, const u64* out_off,
+                         const u32* out_cap, u32* out_len, i32* status,
+                         u32 flags, hipStream_t stream);
+hipError_t launch_headers(const u8* in, const u64* in_off, const u32* in_len,
+                          u32 n_msgs, u32* ulen, int lenient, hipStream_t stream);
+hipError_t launch_decode_v3(const u8* in, const u64* in_off, const u32* in_len,
+                            u32 n_msgs, u8* out, const u64* out_off,
+                            const u32* out_cap, u32* out_len, i32* status,
+                            u32 flags, hipStream_t stream);
+hipError_t launch_decode_v4(const u8* in, const u64* in_off, const u32* in_len,
+                            u32 n_msgs, u8* out, const u64* out_off,
+                            const u32* out_cap, u32* out_len, i32* status,
+                            u32 flags, void* ws, size_t ws_bytes, hipStream_t stream,
+                            int exec_variant, hipStream_t pass1_stream);
+hipError_t launch_decode_partial(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u32 frag,
+                                 u8* out, const u64* out_off, const u32* out_cap, u32* got, u64* produced,
+                                 i32* status, hipStream_t stream);
+hipError_t launch_iov_scatter(const u8* in, const u64* in_off, const u32* in_len, const u8* stage,
+                              const u64* stage_off, const u32* out_len, u32 n_msgs, const u64* iov_base,
+                              const u64* iov_len, const u32* iov_first, i32* status, hipStream_t stream);
+
+// ---- Snappy encode
+size_t encode_tables_workspace_bytes(u32 n_msgs, u32 max_in_len, u32* slots_out);
+size_t encode_plan_bytes(u32 n_msgs, u32 max_in_len);
+hipError_t launch_encode_v3(const u8* in, const u64* in_off, const u32* in_len,
+                            u32 n_msgs, u32 max_in_len, u8* out, const u64* out_off,
+                            u32* out_len, i32* status, void* ws, size_t ws_bytes,
+                            u32 slots, u32 entries, size_t tables_bytes, u32 region_cap,
+                            hipStream_t stream, u32 wave_min);
+hipError_t launch_encode(const u8* in, const u64* in_off, const u32* in_len,
+                         u32 n_msgs, u32 max_in_len, u8* out, const u64* out_off,
+                         u32* out_len, i32* status, hipStream_t stream);
+u32 encode_v3_wave_min(u32 n_msgs, u32 max_in_len, size_t ws_bytes, size_t tables_bytes, u32 wave_min,
+                       bool* planned);
+void encode_v3_wave_split(u32* share_permille, u64* all_bytes);
+
+// ---- gather, pack
+hipError_t launch_gather_blocks(const u64* src, const u32* len, const u64* dst_off, u32 n, u8* dst,
+                                hipStream_t stream);
+size_t pack_workspace_bytes(u32 n_msgs);
+hipError_t launch_pack(const u8* src, const u64* src_off, const u32* len, const i32* status, u32 n, u32 align,
+                       u8* dst, u64* pack_off, u64* total, void* ws, hipStream_t stream);
+
+// ---- LZ4
+// LZ4 compress (lz4_encode_wave.hip): bodies of at least wave_min bytes go to
+// the wave encoder; kLz4WaveNone = none do
+constexpr u64 kLz4WaveNone = 1ull << 32;
+size_t lz4_compress_workspace_bytes(u32 n_msgs);
+size_t lz4_compress_tables_bytes(u32 n_msgs);  // the lanes' tables alone: the workspace before the wave encoder
+hipError_t launch_lz4_encode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
+                             const u64* out_off, u32* out_len, i32* status, void* ws, size_t ws_bytes, u64 wave_min,
+                             hipStream_t stream);
+hipError_t launch_lz4_encode_lanes(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
+                                   const u64* out_off, u32* out_len, i32* status, void* tables, u64 wave_min,
+                                   hipStream_t stream);
+hipError_t launch_lz4_decode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
+                             const u64* out_off, const u32* out_cap, u32* out_len, i32* status,
+                             hipStream_t stream);
+hipError_t launch_lz4_decode_fallback(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
+                                      const u64* out_off, const u32* out_cap, u32* out_len, i32* status,
+                                      u32* fb_count, hipStream_t stream);
+size_t lz4_decode_workspace_bytes(u32 n_msgs, u64 total_in_bytes);
+u64 lz4_decode_bitmap_capacity_words(u32 n_msgs, size_t ws_bytes);
+hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
+                              const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
+                              size_t ws_bytes, hipStream_t stream, hipStream_t pass1_stream);
+
+// ---- path report (capi.hip: fsg_decompress_report and its kin): what each
+// codec's 256-byte workspace header holds after a call, read from a host copy
+struct DecodeHeaderCounts {
+  u32 bitmap_words;  // the bump allocator's final value
+  u32 large, huge;   // messages listed for the wave-per-message index pass
+  u32 fallback, fallback_bitmap, fallback_wide, fallback_guard;  // pass 3 and its causes
+};
+struct EncodeHeaderCounts {
+  u32 units, split, fallback;
+  u64 unit_bytes;
+};
+struct Lz4EncodeHeaderCounts {
+  u32 listed, wave_messages;
+  u64 wave_bytes;
+};
+void decode_v4_header_counts(const void* header, DecodeHeaderCounts* c);
+void encode_v3_header_counts(const void* header, EncodeHeaderCounts* c);
+void lz4_decode_header_counts(const void* header, DecodeHeaderCounts* c);
+void lz4_encode_header_counts(const void* header, Lz4EncodeHeaderCounts* c);
+
+}  // namespace fsg

@@ -18,6 +18,7 @@
 // serial greedy chain.  Position tables live in the workspace (16 KiB per
 // message), zeroed by the launch.  Compress also has a wave per body for the
 // large ones: lz4_encode_wave.hip, which holds the call's routing.
+#include "launch.h"
 #include "snappy_device.h"
 
 namespace fsg {

@@ -44,14 +44,12 @@
 #include <cstdlib>
 #include <mutex>
 
+#include "launch.h"
+#include "launch_util.h"
 #include "options.h"
 #include "wave_util.h"
 
 namespace fsg {
-
-hipError_t launch_lz4_decode_fallback(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
-                                      const u64* out_off, const u32* out_cap, u32* out_len, i32* status,
-                                      u32* fb_count, hipStream_t stream);
 
 namespace {
 
@@ -1182,18 +1180,8 @@ struct L4Two {
   hipEvent_t pass1 = nullptr;
   std::mutex mu;
 };
-L4Two* l4_two() {
-  constexpr int kMaxDevices = 64;
-  static L4Two g[kMaxDevices];
-  static std::once_flag once[kMaxDevices];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
-  L4Two* t = &g[dev];
-  std::call_once(once[dev], [t] {
-    if (hipEventCreateWithFlags(&t->pass1, hipEventDisableTiming) != hipSuccess) t->pass1 = nullptr;
-  });
-  return t->pass1 ? t : nullptr;
-}
+bool create_l4_two(L4Two* t) { return hipEventCreateWithFlags(&t->pass1, hipEventDisableTiming) == hipSuccess; }
+L4Two* l4_two() { return per_device<L4Two>(create_l4_two); }
 }  // namespace
 
 hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
@@ -1209,12 +1197,7 @@ hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len
   hipStream_t s1 = two ? pass1_stream : stream;
   hipError_t e = hipSuccess;
   if (pass1_stream && pass1_stream != stream && !two) {  // no event: order stream behind pass1_stream
-    hipEvent_t ev = nullptr;
-    e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(ev, pass1_stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(stream, ev, 0);
-    if (ev) (void)hipEventDestroy(ev);
-    if (e != hipSuccess) return e;
+    if ((e = order_after(stream, pass1_stream)) != hipSuccess) return e;
   }
   u8* w = static_cast<u8*>(ws);
   u32* counter = reinterpret_cast<u32*>(w);

@@ -35,6 +35,7 @@
 // inside the body's slot.  CPU model, checked block for block against the
 // oracle: tools/l4wenc_model.cc.
 #include "options.h"
+#include "launch.h"
 #include "snappy_device.h"
 
 namespace fsg {
@@ -352,10 +353,6 @@ __global__ __launch_bounds__(64) void lz4_encode_wave_kernel(const u8* __restric
 }
 
 }  // namespace
-
-hipError_t launch_lz4_encode_lanes(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
-                                   const u64* out_off, u32* out_len, i32* status, void* tables, u64 wave_min,
-                                   hipStream_t stream);
 
 // ---- routing (capi.hip: fsg_lz4_compress_batch and fsg_lz4_compress_report)
 size_t lz4_compress_workspace_bytes(u32 n_msgs) { return kHead + list_bytes(n_msgs) + (size_t)n_msgs * kTableBytes; }

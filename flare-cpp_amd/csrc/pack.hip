@@ -20,6 +20,7 @@
 //         hundred bytes next to bodies of megabytes (CM, C5) load every wave
 //         alike, where a wave per message would serialise on the large ones.
 #include "../../include/flare_snappy_gpu.h"
+#include "launch.h"
 #include "snappy_device.h"
 #include "wave_util.h"
 

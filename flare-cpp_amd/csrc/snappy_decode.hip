@@ -11,6 +11,7 @@
 // lane ever reads or writes another lane's bytes and no cross-lane ordering
 // is needed.  Writes never pass the slot's expected length (the reference's
 // 16-byte over-writes are only taken when the space-left checks allow).
+#include "launch.h"
 #include "snappy_lane_decode.h"
 
 namespace fsg {

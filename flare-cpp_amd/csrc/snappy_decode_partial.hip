@@ -43,6 +43,7 @@
 //     TryFastAppend (:1035-1049) where no later tag overwrote it.  The lane
 //     walks byte by byte: a rejected message of L output bytes costs O(L)
 //     serial byte operations on one lane (a 64 KiB body ~3 ms).
+#include "launch.h"
 #include "snappy_device.h"
 
 namespace fsg {

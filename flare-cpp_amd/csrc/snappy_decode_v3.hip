@@ -28,6 +28,7 @@
 // Reference checks and statuses are exactly those of decode_lane_kernel
 // (DecompressAllTags snappy.cc:716-787, writer checks :1141-1481,
 // result :858-868).
+#include "launch.h"
 #include "snappy_pieces.h"
 
 namespace fsg {

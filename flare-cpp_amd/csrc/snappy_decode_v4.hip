@@ -44,7 +44,13 @@
 #include <atomic>
 #include <mutex>
 
+#include "decode_v4_plan.h"
+#include "launch.h"
+#include "launch_util.h"
+
 namespace fsg {
+
+static_assert(kWave == 64, "idx_lean_lds_bytes (decode_v4_plan.h) counts 64 lanes per wave");
 
 namespace {
 
@@ -63,48 +69,21 @@ constexpr int kIdxTagsOne = 32, kIdxTagsPlanned = 24;
 // Rounds B with pattern chunks outside the common path (see exec5_message).
 constexpr u32 kRingChunks = 16;              // 16-byte chunks per lane (256 B)
 constexpr u32 kAhead = 7;                    // chunks prefetched per iteration
-// Waves per pass-1 workgroup.  One: most resident waves for large batches
-// (CM 15.1 ms vs 17.9 with four).  Four (82 KB of LDS: one workgroup per CU,
-// one wave per SIMD) pins the placement and makes the pass insensitive to the
-// launches before it (launch-order effect); C3 the same
-// either way (7.81 vs 7.84 ms).
-#ifndef FSG_IDX_WAVES
-#define FSG_IDX_WAVES 1
-#endif
-constexpr u32 kIdxWaves = FSG_IDX_WAVES;
-static_assert(kIdxWaves == 1 || kIdxWaves == 2 || kIdxWaves == 4, "tag table init");
-// The one-stream lane walk of batches of short bodies (mean compressed size
-// < 16 KiB, e.g. C2) runs four waves per workgroup so its bitmap allocation
-// takes one device-scope atomic per workgroup instead of one per wave: C2
-// 0.1354 -> 0.1276 ms; with long walks (C3) the one-wave blocks stay ahead
-// (6.02 vs 6.06 ms).
-#ifndef FSG_IDX_WAVES_SERIAL
-#define FSG_IDX_WAVES_SERIAL 4
-#endif
-constexpr u32 kIdxWavesSerial = FSG_IDX_WAVES_SERIAL;
-static_assert(kIdxWavesSerial == 1 || kIdxWavesSerial == 2 || kIdxWavesSerial == 4, "tag table init");
+// (kIdxWaves, kIdxWavesSerial -- waves per pass-1 workgroup --, the size
+// thresholds kBigIndexMin/Max and kHugeIndexBytes, kWavesPerBlock and
+// kSingleLiteral: decode_v4_plan.h, with the launch arithmetic that uses them)
 
 // ---- pass 1b (index_big_message, run by exec_kernel's large-message waves) geometry
-constexpr u32 kBigIndexMin = 8 * 1024;       // large: compressed size above
-constexpr u32 kBigIndexMax = 48 * 1024;      // clamp(4 x the batch mean, min, max)
-#ifndef FSG_HUGE_KB
-#define FSG_HUGE_KB 256
-#endif
-constexpr u32 kHugeIndexBytes = FSG_HUGE_KB * 1024;  // large ones handed out first (forked: chunked walk)
 constexpr u32 kBigStageChunks = 5 * 64;      // 16-byte chunks staged per wave
 constexpr u32 kBigStageBytes = 16 * kBigStageChunks;
 
 // ---- pass 2 geometry
-constexpr u32 kWavesPerBlock = 4;
 #ifndef FSG_TAG_RING
 #define FSG_TAG_RING 512
 #endif
 constexpr u32 kTagRing = FSG_TAG_RING;       // tag positions per wave (LDS)
 constexpr u32 kFillWords = kTagRing / 32;    // bitmap words per fill (<= kTagRing / 2 tags)
 constexpr u32 kMaxPieces = 64;
-// bm_base[m] with this bit set: the message is one literal starting at the
-// low bits (set by pass 1; bitmap bases stay below 2^31 words)
-constexpr u32 kSingleLiteral = 0x80000000u;
 
 __device__ u32x4 g_dummy_chunk[1];
 
@@ -230,8 +209,8 @@ __device__ __forceinline__ i32 index_prologue(
   return status;
 }
 
-// Size classes of the planned lane walk (see index_plan_kernel).
-constexpr u32 kWalkClasses = 16;
+// Size classes of the planned lane walk (kWalkClasses of them, see
+// index_plan_kernel).
 __device__ __forceinline__ u32 walk_class(u32 n_in) {
   const u32 lg = 31u - (u32)__builtin_clz(n_in | 1u);
   return kWalkClasses - 1 - (lg < kWalkClasses - 1 ? lg : kWalkClasses - 1);
@@ -240,8 +219,7 @@ __device__ __forceinline__ u32 walk_class(u32 n_in) {
 // Pass 1 plan (batches whose large messages are indexed on a side stream):
 // the prologue alone, so pass 1b can start on the listed large messages while
 // the lane walk (index_kernel<true>) runs; lanes left for the walk get
-// kNeedLaneWalk.
-constexpr u32 kPlanThreads = 1024;
+// kNeedLaneWalk.  (kPlanThreads per block.)
 __global__ __launch_bounds__(kPlanThreads) void index_plan_kernel(
     const u8* __restrict__ in, const u64* __restrict__ in_off,
     const u32* __restrict__ in_len, u32 n_msgs, const u32* __restrict__ out_cap,
@@ -889,10 +867,7 @@ __global__ __launch_bounds__(4 * 64) void index_big_kernel(
 //          rules of index_big_message.
 //   final  one wave per message: status and pass 2's work lists.
 // ===========================================================================
-constexpr u32 kChunkBytes = 32 * 1024;  // a multiple of 512: chunks own whole bitmap words
-struct ChunkRec {
-  u32 m, k, exit, bad, len, base, flags, nchunks;
-};
+// (kChunkBytes and ChunkRec: decode_v4_plan.h, which sizes the record region)
 constexpr u32 kChunkBad = 1, kChunkNoSeg = 2;
 
 namespace {
@@ -1369,26 +1344,8 @@ __global__ __launch_bounds__(4 * 64) void chunk_final_kernel(
 // it.  Literals longer than 64 bytes bypass it: the wave copies them
 // global-to-global, 1 KiB per instruction.
 // ===========================================================================
-namespace {
-// A/B knobs of the execution pass
-// The software-pipelined execution pass (exec6_message; A/B variant).
-// Window and kept history: 3 KiB / 1 KiB at 7 waves per SIMD (C3 6.35 ->
-// 6.20 ms against 4 KiB / 2 KiB at 6 waves, A/B on one box; 4 KiB / 1 KiB
-// at 6 waves 6.33, a 256-entry tag ring 7.04).
-#ifndef FSG_WINDOW
-#define FSG_WINDOW 3072
-#define FSG_KEEP 1024
-#endif
-constexpr u32 kWindow = FSG_WINDOW;  // LDS output window per wave
-constexpr u32 kKeep = FSG_KEEP;      // history kept when the window slides
-// After a slide op - sbase <= keep + 15; a group adds <= 16 * kMaxPieces
-// bytes and an OR store writes up to 20 bytes past a piece's start, all of
-// which must stay inside the window's kWindow + 32 bytes.
-constexpr u32 kMaxKeep = (kWindow - 16 * 64 - 48) & ~15u;
-static_assert(kKeep <= kMaxKeep, "kept history leaves room for one group");
-
-
-}  // namespace
+// (The window constants kWindow, kKeep and kMaxKeep: decode_v4_plan.h, which
+// range-checks option exec_keep against them.)
 
 // A far copy's 16 source bytes: output this wave stored in an earlier group,
 // read from the slot with an sc1 load, which is served by L2 and bypasses
@@ -2218,9 +2175,8 @@ __device__ __forceinline__ void exec5_message(
 #endif
 namespace {
 constexpr u32 kFirstTag = 1u << 23;
-// Path report: the packed pass counts the bodies it hands to pass 3 in the
-// workspace header, at these u32 slots after its batch counter (kWsPackNext).
-constexpr u32 kPackCtrWide = 3, kPackCtrGuard = 4;
+// (kPackCtrWide, kPackCtrGuard -- the path report's slots after the batch
+// counter --: decode_v4_plan.h, with the workspace header's layout)
 constexpr u32 kMidLit = 896;  // literals up to this length run inside a packed group (56 chunks)
 __device__ __forceinline__ u32 lane_bperm(u32 v, u32 src) {
   return (u32)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v);
@@ -2921,82 +2877,6 @@ __global__ __launch_bounds__(64) void fallback_kernel(
   status[m] = decode_one(ib + h, ib + n_in, out + out_off[m], out_len[m], true);
 }
 
-// Workspace layout (bytes from the start; every counter a u32, zeroed by the
-// launch's one fill together with the lists):
-//   [0, 256)  counters, at the kWs* offsets below
-//   then kListBases arrays of base_bytes = round_up(4 n, 256) bytes each:
-//     0 bm_base[n] | 1 big_list[n] | 2-3 seg_list[n] (u64) | 4 whole_list[n] |
-//     5 walk_rank[n] | 6 walk_perm[n] | 7 walk_hist (16 classes + count) |
-//     8-9 seg_list2[n] (u64) | 10 whole_list2[n]
-//   then the tag-start bitmap words.
-// Set 0 = every large message (one stream) or the non-huge ones (forked);
-// set 1 = the huge ones (forked, second side stream).
-constexpr u32 kWsBmCounter = 0;        // bitmap bump allocator
-constexpr u32 kWsSet1BigNext = 16;     // set 1: pass-1b work counter
-constexpr u32 kWsSet1SegCount = 32;    // set 1: segment count
-constexpr u32 kWsSet1WholeCount = 48;  // set 1: whole-message count
-constexpr u32 kWsBigCount = 64;        // large-message count (huge count at +32: big_count + 8)
-constexpr u32 kWsHugeCount = kWsBigCount + 32;
-constexpr u32 kWsSet0BigNext = 128;
-constexpr u32 kWsSet0SegCount = 160;
-constexpr u32 kWsSet0ExecNext = 192;   // pass-2 queue head
-constexpr u32 kWsSet0WholeCount = 224;
-constexpr u32 kWsSet1ExecNext = 240;
-constexpr u32 kWsChunkCount = 80;      // chunked pass 1b: records listed
-constexpr u32 kWsChunkSpecNext = 84;   //   work counters of its passes
-constexpr u32 kWsChunkFixNext = 88;
-constexpr u32 kWsChunkCheckNext = 92;
-constexpr u32 kWsChunkFinalNext = 100;
-constexpr u32 kWsPackNext = 104;      // packed execution: batch counter
-// path report (fsg_decompress_report): pass 3's message count, then its
-// causes -- bitmap overflow (counted by pass 3), the packed pass's 32-bit
-// offset check and its iteration guard (counted where the packed pass marks)
-constexpr u32 kWsFallbackCount = 108;
-constexpr u32 kWsFallbackBitmap = 112;
-constexpr u32 kWsFallbackWide = kWsPackNext + 4 * kPackCtrWide;
-constexpr u32 kWsFallbackGuard = kWsPackNext + 4 * kPackCtrGuard;
-static_assert(kWsFallbackBitmap == kWsFallbackCount + 4, "fallback_kernel counts at fb_count[0..1]");
-constexpr u32 kWsCounterBytes = 256;
-// the counters are distinct u32 slots inside the 256-byte header
-constexpr u32 kWsOffsets[] = {kWsBmCounter, kWsSet1BigNext, kWsSet1SegCount, kWsSet1WholeCount, kWsBigCount,
-                              kWsHugeCount, kWsSet0BigNext, kWsSet0SegCount, kWsSet0ExecNext, kWsSet0WholeCount,
-                              kWsSet1ExecNext, kWsChunkCount, kWsChunkSpecNext, kWsChunkFixNext,
-                              kWsChunkCheckNext, kWsChunkFinalNext, kWsPackNext, kWsFallbackCount,
-                              kWsFallbackBitmap, kWsFallbackWide, kWsFallbackGuard};
-constexpr bool ws_offsets_ok() {
-  for (u32 i = 0; i < sizeof(kWsOffsets) / sizeof(kWsOffsets[0]); ++i) {
-    if (kWsOffsets[i] % 4 || kWsOffsets[i] + 4 > kWsCounterBytes) return false;
-    for (u32 j = 0; j < i; ++j)
-      if (kWsOffsets[i] < kWsOffsets[j] + 4 && kWsOffsets[j] < kWsOffsets[i] + 4) return false;
-  }
-  return true;
-}
-static_assert(ws_offsets_ok(), "workspace counters overlap or leave the header");
-constexpr u64 kListBases = 11;  // u32 arrays of n entries before the bitmap
-// The chunked pass 1b's records live at the workspace's end: 1/64 of it
-// (>= 40 bytes per 20 KiB of input: one 32-byte record per 32 KiB chunk plus
-// two words per huge message).
-constexpr u64 kChunkRegionDiv = 64;
-size_t decode_v4_workspace_bytes(u32 n_msgs, u64 total_in_bytes) {
-  const u64 base_bytes = (4ull * n_msgs + 255) & ~255ull;
-  const u64 words = total_in_bytes / 32 + 4ull * n_msgs + 64;
-  const u64 base = 256 + kListBases * base_bytes + 4 * words;
-  return (size_t)(base + base / (kChunkRegionDiv - 1) + 512);
-}
-
-// The tag-start bitmap's capacity in words: what the fixed part and the chunk
-// records (at the end, 256-byte aligned whatever ws_bytes: the passes load
-// them with scalar loads, which ignore the low address bits) leave.  Shared by
-// the launch and the path report.  ws_bytes >= decode_v4_workspace_bytes(n, 0).
-u64 decode_v4_bitmap_capacity_words(u32 n_msgs, size_t ws_bytes) {
-  const u64 base_bytes = (4ull * n_msgs + 255) & ~255ull;
-  const u64 chunk_bytes = (ws_bytes / kChunkRegionDiv) & ~255ull;
-  const u64 chunk_off = (ws_bytes - chunk_bytes) & ~255ull;
-  u64 cap_words = (chunk_off - 256 - kListBases * base_bytes) / 4;
-  if (cap_words >= kSingleLiteral) cap_words = kSingleLiteral - 1;  // bases < 2^31 words
-  return cap_words;
-}
-
 void decode_v4_header_counts(const void* header, DecodeHeaderCounts* c) {
   u32 ctr[kWsCounterBytes / 4];
   __builtin_memcpy(ctr, header, sizeof(ctr));
@@ -3009,6 +2889,8 @@ void decode_v4_header_counts(const void* header, DecodeHeaderCounts* c) {
   c->fallback_wide = at(kWsFallbackWide);
   c->fallback_guard = at(kWsFallbackGuard);
 }
+
+namespace {
 
 // Per-device side stream and fork/join events for launch_decode_v4 (created
 // on first use; the mutex orders each call's record/wait pairs when several
@@ -3024,33 +2906,262 @@ struct SideStream {
   hipEvent_t pass1 = nullptr;  // two-stream calls: pass 1 done (fsg_decompress_batch_2s)
   std::mutex mu;
 };
-static SideStream* side_stream() {
-  constexpr int kMaxDevices = 64;
-  static SideStream g_side[kMaxDevices];
-  static std::once_flag g_once[kMaxDevices];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
-  SideStream* s = &g_side[dev];
-  std::call_once(g_once[dev], [s] {
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&s->fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s->join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s->pass1, hipEventDisableTiming) != hipSuccess)
-      s->stream = nullptr;
-    // optional second side stream (the huge messages of a forked batch)
-    if (s->stream && (hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking) != hipSuccess ||
-                      hipEventCreateWithFlags(&s->join2, hipEventDisableTiming) != hipSuccess))
-      s->stream2 = nullptr;
-    if (s->stream && (hipStreamCreateWithFlags(&s->stream3, hipStreamNonBlocking) != hipSuccess ||
-                      hipEventCreateWithFlags(&s->join3, hipEventDisableTiming) != hipSuccess))
-      s->stream3 = nullptr;
-  });
-  return s->stream ? s : nullptr;
+bool create_side_stream(SideStream* s) {
+  if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&s->fork, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&s->join, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&s->pass1, hipEventDisableTiming) != hipSuccess)
+    return false;
+  // optional second side stream (the huge messages of a forked batch)
+  if (hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&s->join2, hipEventDisableTiming) != hipSuccess)
+    s->stream2 = nullptr;
+  if (hipStreamCreateWithFlags(&s->stream3, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&s->join3, hipEventDisableTiming) != hipSuccess)
+    s->stream3 = nullptr;
+  return true;
+}
+SideStream* side_stream() { return per_device<SideStream>(create_side_stream); }
+
+// pass 1b's large messages land in pass 2's work lists.  set 0: every large
+// message (one stream) or the non-huge ones (forked); set 1: the huge ones
+// (forked, second side stream), with their own counters and lists.
+struct BigSet {
+  u32 *big_next, *seg_count, *whole_count, *exec_next;
+  u64* seg_list;
+  u32* whole_list;
+};
+
+// pass 2: one tag per lane (5) or <= 16-byte pieces per lane (4)
+using ExecKernel = decltype(&exec_kernel<5>);
+// (Defined ahead of the other launch functions: the compiler emits template
+// instances in the order of their first use, and the measurements in
+// DESIGN.md section 5 were taken with exec_kernel<4>, <5> ahead of the
+// index_kernel instances in the code object.)
+ExecKernel exec_kernel_variant(int v) { return v == 4 ? &exec_kernel<4> : &exec_kernel<5>; }
+
+// One call's arrays: the caller's, and the workspace regions at the plan's
+// offsets.
+struct DecodeBufs {
+  const u8* in;
+  const u64* in_off;
+  const u32* in_len;
+  u32 n_msgs;
+  u8* out;
+  const u64* out_off;
+  const u32* out_cap;
+  u32* out_len;
+  i32* status;
+  u32 flags;
+  ExecKernel ek;
+  u8* w;  // the workspace (counters at the kWs* offsets)
+  u32 *counter, *big_count, *bm_base, *big_list;
+  // the planned lane walk's order: ranks, the permutation, class counts and
+  // offsets (+ the walk count)
+  u32 *walk_rank, *walk_perm, *walk_hist;
+  u32* bitmap;
+  BigSet set0, set1;
+  // chunked pass 1b's record region
+  u32 *first_rec, *mstat;
+  ChunkRec* recs;
+  u32* ctr(u32 off) const { return reinterpret_cast<u32*>(w + off); }
+};
+
+void workspace_pointers(const DecodePlan& p, void* ws, DecodeBufs* b) {
+  u8* w = static_cast<u8*>(ws);
+  auto words = [w](u64 off) { return reinterpret_cast<u32*>(w + off); };
+  b->w = w;
+  b->counter = words(kWsBmCounter);
+  b->big_count = words(kWsBigCount);
+  b->bm_base = words(p.bm_base_off);
+  b->big_list = words(p.big_list_off);
+  b->walk_rank = words(p.walk_rank_off);
+  b->walk_perm = words(p.walk_perm_off);
+  b->walk_hist = words(p.walk_hist_off);
+  b->bitmap = words(p.bitmap_off);
+  b->set0 = BigSet{words(kWsSet0BigNext), words(kWsSet0SegCount), words(kWsSet0WholeCount), words(kWsSet0ExecNext),
+                   reinterpret_cast<u64*>(w + p.seg_list_off), words(p.whole_list_off)};
+  b->set1 = BigSet{words(kWsSet1BigNext), words(kWsSet1SegCount), words(kWsSet1WholeCount), words(kWsSet1ExecNext),
+                   reinterpret_cast<u64*>(w + p.seg_list2_off), words(p.whole_list2_off)};
+  b->first_rec = words(p.first_rec_off);
+  b->mstat = words(p.mstat_off);
+  b->recs = reinterpret_cast<ChunkRec*>(w + p.recs_off);
 }
 
-// Dynamic LDS of the lean lane walk: per wave an 8-chunk input ring (+5
-// dwords) and 2 bit groups, [dword][lane]; the 256-entry tag table.
-constexpr size_t idx_lean_lds_bytes() { return 4 * (kIdxWaves * (8 * 4 + 5 + 8) * kWave + 256); }
+// The lane walk: planned (after index_plan_kernel; part 1 / 2: one side of
+// the split walk) or the plan's one-stream instance.
+hipError_t launch_index(const DecodePlan& p, const DecodeBufs& b, bool planned, hipStream_t st, u32 part = 0) {
+  const LaunchDim& d = planned ? p.planned_walk : p.walk;
+  if (planned)
+    index_kernel<true><<<d.grid, d.block, d.lds, st>>>(
+        b.in, b.in_off, b.in_len, b.n_msgs, b.out_cap, b.out_len, b.status, b.flags, b.counter, b.bm_base, b.bitmap,
+        p.cap_words, b.big_count, b.big_list, p.big_threshold, p.walk_order ? b.walk_perm : nullptr, b.walk_hist,
+        part, p.split_class);
+  else if (p.walk_kind == kWalkLean)
+    index_kernel<false, true><<<d.grid, d.block, d.lds, st>>>(
+        b.in, b.in_off, b.in_len, b.n_msgs, b.out_cap, b.out_len, b.status, b.flags, b.counter, b.bm_base, b.bitmap,
+        p.cap_words, b.big_count, b.big_list, p.big_threshold, nullptr, nullptr);
+  else if (p.walk_kind == kWalkSerial)
+    index_kernel<false, false, kIdxWavesSerial><<<d.grid, d.block, d.lds, st>>>(
+        b.in, b.in_off, b.in_len, b.n_msgs, b.out_cap, b.out_len, b.status, b.flags, b.counter, b.bm_base, b.bitmap,
+        p.cap_words, b.big_count, b.big_list, p.big_threshold, nullptr, nullptr);
+  else
+    index_kernel<false><<<d.grid, d.block, d.lds, st>>>(
+        b.in, b.in_off, b.in_len, b.n_msgs, b.out_cap, b.out_len, b.status, b.flags, b.counter, b.bm_base, b.bitmap,
+        p.cap_words, b.big_count, b.big_list, p.big_threshold, nullptr, nullptr);
+  return hipGetLastError();
+}
+
+// pass 1b: large messages, one wave each (an empty list costs one short
+// launch); they land in set s of pass 2's work lists.
+hipError_t launch_index_big(const DecodePlan& p, const DecodeBufs& b, hipStream_t st, const BigSet& s, u32 mode) {
+  index_big_kernel<<<p.index_big_grid, 256, 0, st>>>(
+      b.in, b.in_off, b.in_len, b.out_len, b.flags, b.status, b.bm_base, b.bitmap, b.big_count, b.big_list,
+      s.big_next, b.n_msgs, b.out, b.out_off, s.seg_list, s.seg_count, s.whole_list, s.whole_count, mode);
+  return hipGetLastError();
+}
+
+// The forked path's large-message exec launch: the large-message blocks only
+// (exit after one atomic when the lists are empty).
+hipError_t launch_big_exec(const DecodePlan& p, const DecodeBufs& b, hipStream_t st, const BigSet& s) {
+  b.ek<<<p.fork_big_blocks, kWavesPerBlock * 64, 0, st>>>(
+      b.in, b.in_off, b.in_len, b.n_msgs, b.out, b.out_off, b.out_len, b.status, b.bm_base, b.bitmap,
+      reinterpret_cast<const u32*>(s.seg_list), s.seg_count, s.whole_list, s.whole_count, s.exec_next,
+      p.fork_big_blocks, p.big_threshold, 0u, p.keep_hist, 0u, nullptr, nullptr, 0u, 0u);
+  return hipGetLastError();
+}
+
+hipError_t launch_big(const DecodePlan& p, const DecodeBufs& b, hipStream_t st, const BigSet& s, u32 mode) {
+  const hipError_t e = launch_index_big(p, b, st, s, mode);
+  if (e != hipSuccess) return e;
+  return launch_big_exec(p, b, st, s);
+}
+
+// The huge messages' pass 1b, chunked (chunk_*_kernel; DecodePlan::chunked),
+// then their execution.
+hipError_t launch_big_chunked(const DecodePlan& p, const DecodeBufs& b, hipStream_t st, const BigSet& s) {
+  u32* const cctr = b.ctr(kWsChunkCount);
+  chunk_list_kernel<<<p.chunk_list_grid, 256, 0, st>>>(b.in, b.in_off, b.in_len, b.big_count, b.big_list, b.n_msgs,
+                                                       b.flags, cctr, b.recs, b.first_rec, (u32)p.max_recs);
+  chunk_spec_kernel<<<p.chunk_rec_grid, 256, 0, st>>>(b.in, b.in_off, b.in_len, b.flags, b.bm_base, b.bitmap, cctr,
+                                                      b.recs, b.ctr(kWsChunkSpecNext), (u32)p.max_recs);
+  chunk_fixup_kernel<<<p.chunk_msg_grid, 256, 0, st>>>(b.in, b.in_off, b.in_len, b.out_len, b.bm_base, b.bitmap,
+                                                       b.big_count, b.recs, b.first_rec, b.mstat,
+                                                       b.ctr(kWsChunkFixNext));
+  chunk_check_kernel<<<p.chunk_rec_grid, 256, 0, st>>>(b.in, b.in_off, b.in_len, b.out_len, b.bm_base, b.bitmap, cctr,
+                                                       b.recs, b.out, b.out_off, b.ctr(kWsChunkCheckNext),
+                                                       (u32)p.max_recs);
+  chunk_final_kernel<<<p.chunk_msg_grid, 256, 0, st>>>(b.in, b.in_off, b.in_len, b.flags, b.bm_base, b.bitmap, b.out,
+                                                       b.out_off, b.big_list, b.out_len, b.status, b.big_count,
+                                                       b.recs, b.first_rec, b.mstat, b.n_msgs, s.seg_list,
+                                                       s.seg_count, s.whole_list, s.whole_count,
+                                                       b.ctr(kWsChunkFinalNext));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_big_exec(p, b, st, s);
+}
+
+// The forked path's small-message launch: one wave per message, or a grid of
+// small_grid blocks whose waves loop; large ones are skipped (big_blocks = 0:
+// no block takes the large-message role).  part 1 / 2: the messages of that
+// part of the split walk, in walk order; 3: all of them in walk order.
+hipError_t launch_small(const DecodePlan& p, const DecodeBufs& b, hipStream_t st, u32 part) {
+  b.ek<<<p.small_grid, kWavesPerBlock * 64, 0, st>>>(
+      b.in, b.in_off, b.in_len, b.n_msgs, b.out, b.out_off, b.out_len, b.status, b.bm_base, b.bitmap,
+      reinterpret_cast<const u32*>(b.set0.seg_list), b.set0.seg_count, b.set0.whole_list, b.set0.whole_count,
+      b.set0.exec_next, 0u, p.big_threshold, 0u, p.keep_hist, p.small_stride, part ? b.walk_perm : nullptr,
+      part ? b.walk_hist : nullptr, part, p.split_class);
+  return hipGetLastError();
+}
+
+// The short bodies of walk part 2 packed several to a wave (exec5_packed).
+hipError_t launch_packed(const DecodePlan& p, const DecodeBufs& b, hipStream_t st) {
+  exec_packed_kernel<<<p.small_grid, kWavesPerBlock * 64, 0, st>>>(
+      b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_len, b.status, b.bm_base, b.bitmap, b.walk_perm, b.walk_hist,
+      p.split_class, b.ctr(kWsPackNext), p.pack_batch, p.keep_hist);
+  return hipGetLastError();
+}
+
+// The forked path: the plan pass lists the large messages; pass 1b starts on
+// them (side streams) while the lane walk and the small messages' execution
+// run on `stream`; all streams join on `stream`.
+hipError_t launch_forked(const DecodePlan& p, const DecodeBufs& b, SideStream* side, hipStream_t stream) {
+  hipError_t e;
+  index_plan_kernel<<<p.plan_grid, kPlanThreads, 0, stream>>>(
+      b.in, b.in_off, b.in_len, b.n_msgs, b.out_cap, b.out_len, b.status, b.flags, b.counter, b.bm_base, b.bitmap,
+      p.cap_words, b.big_count, b.big_list, p.big_threshold, p.walk_order ? b.walk_rank : nullptr, b.walk_hist);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (p.walk_order) {
+    walk_offsets_kernel<<<1, 64, 0, stream>>>(b.walk_hist);
+    walk_scatter_kernel<<<p.scatter_grid, 256, 0, stream>>>(b.in_len, b.n_msgs, b.status, b.walk_rank, b.walk_hist,
+                                                            b.walk_perm);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  // The huge messages (> kHugeIndexBytes compressed) are walked and
+  // executed on a second side stream, so the other large messages'
+  // execution starts when their own (shorter) walks end instead of after
+  // the longest walk: CM 7.6 -> see DESIGN.md section 5.
+  std::lock_guard<std::mutex> lk(side->mu);
+  if ((e = hipEventRecord(side->fork, stream)) != hipSuccess) return e;
+  if ((e = hipStreamWaitEvent(side->stream, side->fork, 0)) != hipSuccess) return e;
+  const bool split = p.split_huge && side->stream2;
+  if (split) {
+    if ((e = hipStreamWaitEvent(side->stream2, side->fork, 0)) != hipSuccess) return e;
+    if ((e = p.chunked ? launch_big_chunked(p, b, side->stream2, b.set1)
+                       : launch_big(p, b, side->stream2, b.set1, 1u)) != hipSuccess)
+      return e;
+    if ((e = hipEventRecord(side->join2, side->stream2)) != hipSuccess) return e;
+  }
+  if ((e = launch_big(p, b, side->stream, b.set0, split ? 2u : 0u)) != hipSuccess) return e;
+  if ((e = hipEventRecord(side->join, side->stream)) != hipSuccess) return e;
+  const bool three = p.split_mode == 1 && p.walk_order && side->stream3;
+  if (three) {
+    // the larger small bodies: walk and execution on the third stream
+    if ((e = hipStreamWaitEvent(side->stream3, side->fork, 0)) != hipSuccess) return e;
+    if ((e = launch_index(p, b, true, side->stream3, 1u)) != hipSuccess) return e;
+    if ((e = launch_small(p, b, side->stream3, 1u)) != hipSuccess) return e;
+    if ((e = hipEventRecord(side->join3, side->stream3)) != hipSuccess) return e;
+    if ((e = launch_index(p, b, true, stream, 2u)) != hipSuccess) return e;
+    if ((e = launch_small(p, b, stream, 2u)) != hipSuccess) return e;
+    if ((e = hipStreamWaitEvent(stream, side->join3, 0)) != hipSuccess) return e;
+  } else {
+    if ((e = launch_index(p, b, true, stream)) != hipSuccess) return e;
+    if (p.walk_order && p.split_mode == 2) {
+      if ((e = launch_small(p, b, stream, 3u)) != hipSuccess) return e;
+    } else if (p.walk_order && p.split_mode == 3) {
+      if ((e = p.pack_batch ? launch_packed(p, b, stream) : launch_small(p, b, stream, 2u)) != hipSuccess) return e;
+      if ((e = launch_small(p, b, stream, 1u)) != hipSuccess) return e;
+    } else {
+      if ((e = launch_small(p, b, stream, 0u)) != hipSuccess) return e;
+    }
+  }
+  if ((e = hipStreamWaitEvent(stream, side->join, 0)) != hipSuccess) return e;
+  if (split && (e = hipStreamWaitEvent(stream, side->join2, 0)) != hipSuccess) return e;
+  return hipSuccess;
+}
+
+// This call's options (csrc/options.h, set with fsg_set_option; never the
+// environment here).
+DecodeOpts read_decode_opts() {
+  DecodeOpts o;
+  o.decode_fork = opt(kOptDecodeFork);
+  o.split_walk = opt(kOptSplitWalk);
+  o.split_class = opt(kOptSplitClass);
+  o.exec_keep = opt(kOptExecKeep);
+  o.chunked_huge = opt(kOptChunkedHuge);
+  o.small_persist = opt(kOptSmallPersist);
+  o.small_batch = opt(kOptSmallBatch);
+  o.split_huge = opt(kOptSplitHuge);
+  o.walk_order = opt(kOptWalkOrder);
+  o.lean_walk = opt(kOptLeanWalk);
+  o.exec_big_blocks = opt(kOptExecBigBlocks);
+  o.exec_prio = opt(kOptExecPrio);
+  o.exec_big_blocks_fork = opt(kOptExecBigBlocksFork);
+  o.exec_pack = opt(kOptExecPack);
+  return o;
+}
+
+}  // namespace
 
 hipError_t launch_decode_v4(const u8* in, const u64* in_off, const u32* in_len,
                             u32 n_msgs, u8* out, const u64* out_off,
@@ -3068,59 +3179,23 @@ hipError_t launch_decode_v4(const u8* in, const u64* in_off, const u32* in_len,
       // No per-device event set: order `stream` behind whatever the caller
       // queued on pass1_stream with a temporary event and run every pass on
       // `stream` (as capi.hip's single-pass path does).
-      hipEvent_t ev = nullptr;
-      hipError_t e0 = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-      if (e0 == hipSuccess) e0 = hipEventRecord(ev, pass1_stream);
-      if (e0 == hipSuccess) e0 = hipStreamWaitEvent(stream, ev, 0);
-      if (ev) (void)hipEventDestroy(ev);
+      const hipError_t e0 = order_after(stream, pass1_stream);
       if (e0 != hipSuccess) return e0;
-      pass1_stream = nullptr;
     }
   }
-  hipStream_t const caller_stream = stream;
-  // planned lane walk in size-class order (FSG_WALK_ORDER=0 disables)
-  // (options: csrc/options.h, set with fsg_set_option; never the environment here)
-  const bool kSplitHuge = opt(kOptSplitHuge) != 0;  // 0: one side stream
-  const bool kWalkOrder = opt(kOptWalkOrder) != 0;
-  // Two-stream form: the lean lane walk (FSG_LEAN_WALK=0: the standard one).
-  // Measured (C3, stream of two alternating batches, one box): lean 6.13 ms
-  // per batch, standard 6.57, serial 6.15; an execution pass made persistent
-  // at 5 or 6 blocks per CU to leave wave slots for the walk: 6.38 / 7.25
-  // (the dispatcher does not spread a persistent grid evenly); the execution
-  // pass held to six blocks per CU by padding its LDS, with a two-wave lean
-  // walk in the space left: 6.32 vs serial 6.11 (the walk's instructions
-  // compete with an execution pass already at the issue limit).
-  const bool kLeanWalk = opt(kOptLeanWalk) != 0;
-  if (two) stream = pass1_stream;  // every pass-1 launch below goes there
-  // pass 2: one tag per lane (5) or <= 16-byte pieces per lane (4)
-  auto* const ek = exec_variant == 4 ? &exec_kernel<4> : &exec_kernel<5>;
-  u8* w = static_cast<u8*>(ws);
-  const u64 base_bytes = (4ull * n_msgs + 255) & ~255ull;
   // the fixed part, the chunk-record region and a bitmap of at least the
   // per-message minimum (decode_v4_workspace_bytes with no input): below it
-  // the region arithmetic below would underflow
+  // the plan's region arithmetic would underflow
   if (ws_bytes < decode_v4_workspace_bytes(n_msgs, 0)) return hipErrorInvalidValue;
-  u32* counter = reinterpret_cast<u32*>(w + kWsBmCounter);
-  u32* big_count = reinterpret_cast<u32*>(w + kWsBigCount);
-  u32* bm_base = reinterpret_cast<u32*>(w + 256);
-  u32* big_list = reinterpret_cast<u32*>(w + 256 + base_bytes);
-  u64* seg_list = reinterpret_cast<u64*>(w + 256 + 2 * base_bytes);
-  u32* whole_list = reinterpret_cast<u32*>(w + 256 + 4 * base_bytes);
-  // the planned lane walk's order: ranks, the permutation, class counts and
-  // offsets (+ the walk count)
-  u32* walk_rank = reinterpret_cast<u32*>(w + 256 + 5 * base_bytes);
-  u32* walk_perm = reinterpret_cast<u32*>(w + 256 + 6 * base_bytes);
-  u32* walk_hist = reinterpret_cast<u32*>(w + 256 + 7 * base_bytes);
-  // the huge messages' pass-2 work lists (forked path, second side stream)
-  u64* seg_list2 = reinterpret_cast<u64*>(w + 256 + 8 * base_bytes);
-  u32* whole_list2 = reinterpret_cast<u32*>(w + 256 + 10 * base_bytes);
-  u32* bitmap = reinterpret_cast<u32*>(w + 256 + kListBases * base_bytes);
-  // chunk records (chunked pass 1b) at the end, the bitmap before them
-  // (decode_v4_bitmap_capacity_words)
-  const u64 chunk_bytes = (ws_bytes / kChunkRegionDiv) & ~255ull;
-  const u64 chunk_off = (ws_bytes - chunk_bytes) & ~255ull;
-  u8* const chunk_region = w + chunk_off;
-  const u64 cap_words = decode_v4_bitmap_capacity_words(n_msgs, ws_bytes);
+
+  // ---- plan, and the pointers at its offsets
+  const DecodePlan p = decode_v4_plan(n_msgs, ws_bytes, two != nullptr, read_decode_opts());
+  DecodeBufs b{in, in_off, in_len, n_msgs, out, out_off, out_cap, out_len, status, flags,
+               exec_kernel_variant(exec_variant)};
+  workspace_pointers(p, ws, &b);
+
+  // ---- fill
+  hipStream_t const s1 = two ? pass1_stream : stream;  // every pass-1 launch goes there
   // zero the counters and the bitmap (pass 1 writes only groups holding
   // tags) with one fill from the counters to the end of the bitmap: the
   // lists between them are 20 B per message (A/B: C2 0.159 -> 0.157 ms, C3
@@ -3128,283 +3203,32 @@ hipError_t launch_decode_v4(const u8* in, const u64* in_off, const u32* in_len,
   // next index pass place its one-wave workgroups unevenly: C3 +0.27 ms)
   // counters and lists only: the passes that write the bitmap store every
   // word the execution pass reads (C3: an 80 us fill of 267 MB saved)
-  hipError_t e = hipMemsetAsync(w, 0, 256 + kListBases * base_bytes, stream);
+  hipError_t e = hipMemsetAsync(b.w, 0, p.bitmap_off, s1);
   if (e != hipSuccess) return e;
-  // Large-message threshold: 4x the batch's mean compressed size (estimated
-  // from the workspace, which callers size from the packed input), clamped
-  // to [8, 48] KiB.  The lane pass's time is its longest message; uniform
-  // batches (C2, C3) send nothing to the wave pass.
-  const u64 est_total_in = cap_words > 4ull * n_msgs + 64 ? (cap_words - 4ull * n_msgs - 64) * 32 : 0;
-  u64 thr = 4 * est_total_in / n_msgs;
-  thr = thr < kBigIndexMin ? kBigIndexMin : (thr > kBigIndexMax ? kBigIndexMax : thr);
-  // A batch of at most one wave of messages (the host runtime's one-caller
-  // batches): the lane walk would be one lane per message, its latency the
-  // longest message's tag chain (~160 us for a 4 KiB text body), where pass
-  // 1b walks each message with a whole wave (a few us).  Every message goes
-  // to pass 1b (option small_batch sets the bound; 0 disables).
-  const i64 kSmallBatch = opt(kOptSmallBatch);
-  if ((i64)n_msgs <= kSmallBatch) thr = 0;
-  const u32 big_threshold = (u32)thr;
-  const u32 idx_blocks = (n_msgs + 64 * kIdxWaves - 1) / (64 * kIdxWaves);
-  // Order of the forked path's small-message execution.  The split point:
-  // bodies of size class >= kSplitClass (compressed size < 2^(16 -
-  // kSplitClass) bytes; option split_class) vs the larger ones.
-  // Option split_walk (A/B): 0 the execution in message order
-  // after one walk; 1 the walk and execution split on two streams (above);
-  // 2 one walk, then the execution in walk order (size classes, largest
-  // first); 3 (default) one walk, then the smaller bodies' execution, then
-  // the larger ones'.  CM, A/B on one box, two rounds, with the chunked
-  // huge-body walk: 0 6.74 / 6.72, 1 (unchunked) 7.54 / 7.45 -- the third
-  // stream shares a hardware queue with the huge bodies' stream and waits
-  // behind it --, 2 6.55 / 6.45, 3 6.45 / 6.44 ms.  In message order a
-  // wave's run of bodies mixes sizes and the launch waits for the waves that
-  // drew the larger ones (execution 4.66 ms; in walk order 3.91).
-  const u32 split_mode = (u32)opt(kOptSplitWalk);
-  const bool split_walk = split_mode == 1;
-  const u32 kSplitClass = (u32)opt(kOptSplitClass) % kWalkClasses;
-  auto launch_index = [&](bool planned, hipStream_t st = nullptr, u32 part = 0) -> hipError_t {
-    if (planned)
-      index_kernel<true><<<idx_blocks, 64 * kIdxWaves, 0, st ? st : stream>>>(
-          in, in_off, in_len, n_msgs, out_cap, out_len, status, flags, counter, bm_base, bitmap,
-          cap_words, big_count, big_list, big_threshold, kWalkOrder ? walk_perm : nullptr, walk_hist, part,
-          kSplitClass);
-    else if (two && kLeanWalk)
-      index_kernel<false, true><<<idx_blocks, 64 * kIdxWaves, idx_lean_lds_bytes(), stream>>>(
-          in, in_off, in_len, n_msgs, out_cap, out_len, status, flags, counter, bm_base, bitmap,
-          cap_words, big_count, big_list, big_threshold, nullptr, nullptr);
-    else if (est_total_in < 16384ull * n_msgs)
-      index_kernel<false, false, kIdxWavesSerial><<<(n_msgs + 64 * kIdxWavesSerial - 1) / (64 * kIdxWavesSerial),
-                                                    64 * kIdxWavesSerial, 0, stream>>>(
-          in, in_off, in_len, n_msgs, out_cap, out_len, status, flags, counter, bm_base, bitmap,
-          cap_words, big_count, big_list, big_threshold, nullptr, nullptr);
-    else
-      index_kernel<false><<<idx_blocks, 64 * kIdxWaves, 0, stream>>>(
-          in, in_off, in_len, n_msgs, out_cap, out_len, status, flags, counter, bm_base, bitmap,
-          cap_words, big_count, big_list, big_threshold, nullptr, nullptr);
-    return hipGetLastError();
-  };
-  // Pass 1b and the large-message exec blocks run on a side stream, after a
-  // plan pass (headers, bitmap bases, the large-message list) and beside the
-  // lane walk and the one-wave-per-message exec launch: pass 1b is bound by
-  // the serial window walk of the few largest bodies and leaves most CUs
-  // idle, which the small messages' passes fill.  Both streams join before
-  // the fallback pass.
-  // Only for batches of > 128K messages (the mixed-size ones): a fork and
-  // join cost ~10 us (C2 0.159 -> 0.169 ms), and uniform batches send nothing
-  // to pass 1b (CM 14.4 -> 12.1 ms).  Option decode_fork 0/1 forces (A/B).
-  const u32 small_blocks = (n_msgs + kWavesPerBlock - 1) / kWavesPerBlock;
-  // A/B knob; at least one block: the large-message lists are only drained there
-  const i64 big_opt = opt(kOptExecBigBlocks);
-  const u32 kBigBlocks = big_opt >= 1 && big_opt <= (1 << 20) ? (u32)big_opt : 512u;
-  const u32 kPrio = opt(kOptExecPrio) != 0 ? 1u : 0u;  // A/B knob: 0 disables the priority raise
-  // history kept when an exec window slides (option exec_keep: the tests
-  // shrink it to exercise the slide's flush rule; 512..kMaxKeep bytes, a
-  // multiple of 16; anything else is the default)
-  u32 keep_hist = kKeep;
-  {
-    const i64 v = opt(kOptExecKeep);
-    if (v >= 512 && v <= (i64)kMaxKeep && v % 16 == 0) keep_hist = (u32)v;
-  }
-  const i64 fork_opt = opt(kOptDecodeFork);
-  const bool fork = !two && (fork_opt >= 0 ? fork_opt != 0 : n_msgs > 131072u);
-  const u32 big_blocks = small_blocks < kBigBlocks ? small_blocks : kBigBlocks;
-  // pass 1b: large messages, one wave each (an empty list costs one short
-  // launch); they land in pass 2's work lists.  set 0: every large message
-  // (one stream) or the non-huge ones (forked); set 1: the huge ones (forked,
-  // second side stream), with their own counters and lists.
-  struct BigSet {
-    u32 *big_next, *seg_count, *whole_count, *exec_next;
-    u64* seg_list;
-    u32* whole_list;
-  };
-  const BigSet set0{reinterpret_cast<u32*>(w + kWsSet0BigNext), reinterpret_cast<u32*>(w + kWsSet0SegCount),
-                    reinterpret_cast<u32*>(w + kWsSet0WholeCount), reinterpret_cast<u32*>(w + kWsSet0ExecNext),
-                    seg_list, whole_list};
-  const BigSet set1{reinterpret_cast<u32*>(w + kWsSet1BigNext), reinterpret_cast<u32*>(w + kWsSet1SegCount),
-                    reinterpret_cast<u32*>(w + kWsSet1WholeCount), reinterpret_cast<u32*>(w + kWsSet1ExecNext),
-                    seg_list2, whole_list2};
-  auto launch_index_big_set = [&](hipStream_t st, const BigSet& b, u32 mode) -> hipError_t {
-    const u32 q = (n_msgs + 3) / 4;
-    const u32 blocks = q < 1024u ? q : 1024u;
-    index_big_kernel<<<blocks, 256, 0, st>>>(
-        in, in_off, in_len, out_len, flags, status, bm_base, bitmap, big_count, big_list,
-        b.big_next, n_msgs, out, out_off, b.seg_list, b.seg_count, b.whole_list, b.whole_count, mode);
-    return hipGetLastError();
-  };
-  auto launch_index_big = [&](hipStream_t st) -> hipError_t { return launch_index_big_set(st, set0, 0u); };
-  // The forked path's large-message launches: CM 9.9 -> 8.85 ms with 1,792
-  // blocks against 512 when they ran alone after the lane walk; 1,024 since
-  // the small bodies' execution (walk order, 3,584 blocks) runs beside them:
-  // CM 6.32-6.37 -> 6.20-6.25 ms for the two grid sizes together (A/B on one
-  // box, four rounds).
-  const i64 bbf_opt = opt(kOptExecBigBlocksFork);  // A/B knob, separate from the one-stream launch's
-  const u32 kBigBlocksFork = bbf_opt >= 1 && bbf_opt <= (1 << 20) ? (u32)bbf_opt : 1024u;
-  auto launch_big = [&](hipStream_t st, const BigSet& b, u32 mode) -> hipError_t {
-    hipError_t e2 = launch_index_big_set(st, b, mode);
-    if (e2 != hipSuccess) return e2;
-    // the large-message blocks only (exit after one atomic when the lists
-    // are empty)
-    const u32 fork_big_blocks = small_blocks < kBigBlocksFork ? small_blocks : kBigBlocksFork;
-    ek<<<fork_big_blocks, kWavesPerBlock * 64, 0, st>>>(
-        in, in_off, in_len, n_msgs, out, out_off, out_len, status, bm_base, bitmap,
-        reinterpret_cast<const u32*>(b.seg_list), b.seg_count, b.whole_list, b.whole_count, b.exec_next,
-        fork_big_blocks, big_threshold, 0u, keep_hist, 0u, nullptr, nullptr, 0u, 0u);
-    return hipGetLastError();
-  };
-  // The huge messages' pass 1b, chunked (chunk_*_kernel): when the record
-  // region holds a batch of this workspace's size (option chunked_huge 0:
-  // one wave per message).  On by default since the small bodies' execution runs
-  // in walk order (FSG_SPLIT_WALK 3): CM 6.77-6.81 -> 6.44 ms, where the
-  // chunked walk alone had measured slower (the huge bodies were then off
-  // the critical path).
-  const bool kChunked = opt(kOptChunkedHuge) != 0;  // (the tests run both forms)
-  // record region: 8 B per possible huge message (its first record, its
-  // chain verdict), then the chunk records -- sized for the batch's bound on
-  // huge messages (est_total_in / kHugeIndexBytes), the records after them
-  const u64 max_huge_need = est_total_in / kHugeIndexBytes + 1;
-  const u64 max_huge = 8 * max_huge_need < chunk_bytes ? max_huge_need : chunk_bytes / 320;
-  const u64 max_recs = max_huge ? (chunk_bytes - 8 * max_huge) / sizeof(ChunkRec) : 0;
-  u32* const first_rec = reinterpret_cast<u32*>(chunk_region);
-  u32* const mstat = first_rec + max_huge;
-  ChunkRec* const recs = reinterpret_cast<ChunkRec*>(chunk_region + 8 * max_huge);
-  const bool chunked = kChunked && max_huge >= est_total_in / kHugeIndexBytes + 1 &&
-                       max_recs >= est_total_in / kChunkBytes + est_total_in / kHugeIndexBytes + 2;
-  auto launch_big_chunked = [&](hipStream_t st, const BigSet& b) -> hipError_t {
-    u32* const cctr = reinterpret_cast<u32*>(w + kWsChunkCount);
-    const u32 lb = (u32)((max_huge + 255) / 256);
-    chunk_list_kernel<<<lb ? lb : 1u, 256, 0, st>>>(in, in_off, in_len, big_count, big_list, n_msgs, flags, cctr,
-                                                     recs, first_rec, (u32)max_recs);
-    const u32 wb = (u32)(max_recs / 4 + 1 < 1024 ? max_recs / 4 + 1 : 1024);
-    chunk_spec_kernel<<<wb, 256, 0, st>>>(in, in_off, in_len, flags, bm_base, bitmap, cctr, recs,
-                                          reinterpret_cast<u32*>(w + kWsChunkSpecNext), (u32)max_recs);
-    const u32 hb = (u32)(max_huge / 4 + 1 < 256 ? max_huge / 4 + 1 : 256);
-    chunk_fixup_kernel<<<hb, 256, 0, st>>>(in, in_off, in_len, out_len, bm_base, bitmap, big_count, recs, first_rec,
-                                           mstat, reinterpret_cast<u32*>(w + kWsChunkFixNext));
-    chunk_check_kernel<<<wb, 256, 0, st>>>(in, in_off, in_len, out_len, bm_base, bitmap, cctr, recs, out, out_off,
-                                           reinterpret_cast<u32*>(w + kWsChunkCheckNext), (u32)max_recs);
-    chunk_final_kernel<<<hb, 256, 0, st>>>(in, in_off, in_len, flags, bm_base, bitmap, out, out_off, big_list,
-                                           out_len, status, big_count, recs, first_rec, mstat, n_msgs, b.seg_list,
-                                           b.seg_count, b.whole_list, b.whole_count,
-                                           reinterpret_cast<u32*>(w + kWsChunkFinalNext));
-    hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) return e2;
-    const u32 fork_big_blocks = small_blocks < kBigBlocksFork ? small_blocks : kBigBlocksFork;
-    ek<<<fork_big_blocks, kWavesPerBlock * 64, 0, st>>>(
-        in, in_off, in_len, n_msgs, out, out_off, out_len, status, bm_base, bitmap,
-        reinterpret_cast<const u32*>(b.seg_list), b.seg_count, b.whole_list, b.whole_count, b.exec_next,
-        fork_big_blocks, big_threshold, 0u, keep_hist, 0u, nullptr, nullptr, 0u, 0u);
-    return hipGetLastError();
-  };
-  // The forked path's small-message launches: a grid of kSmallPersist blocks,
-  // each wave looping over messages; CM 7.31 -> 7.02 ms against one wave per
-  // message (A/B on one box, two passes; 1,024 blocks: 7.11, 3,584: 7.03);
-  // 3,584 (two rounds of blocks at 7 waves per SIMD) since the execution
-  // runs in walk order (see kBigBlocksFork).  Option small_persist (blocks:
-  // the tests shrink it; 0 = one wave per message).
-  const i64 sp_opt = opt(kOptSmallPersist);
-  const u32 kSmallPersist = sp_opt >= 0 && sp_opt <= (1 << 20) ? (u32)sp_opt : 3584u;
-  auto launch_small = [&](hipStream_t st, u32 part) -> hipError_t {
-    // one wave per message; large ones are skipped (big_blocks = 0: no block
-    // takes the large-message role).  part 1 / 2: the messages of that part
-    // of the split walk, in walk order.
-    const u32 grid = kSmallPersist && kSmallPersist < small_blocks ? kSmallPersist : small_blocks;
-    ek<<<grid, kWavesPerBlock * 64, 0, st>>>(
-        in, in_off, in_len, n_msgs, out, out_off, out_len, status, bm_base, bitmap,
-        reinterpret_cast<const u32*>(seg_list), set0.seg_count, whole_list, set0.whole_count, set0.exec_next,
-        0u, big_threshold, 0u, keep_hist, grid < small_blocks ? grid : 0u, part ? walk_perm : nullptr,
-        part ? walk_hist : nullptr, part, kSplitClass);
-    return hipGetLastError();
-  };
-  // The short bodies of walk part 2 packed several to a wave (exec5_packed):
-  // option exec_pack = bodies per batch (1..64, default 32; 0 = one wave per
-  // body, the small-message grid above).  Grid: the small-message grid's
-  // size.  Measured on CM (A/B on one box):
-  // 5.85-5.92 ms against 6.11-6.19 with one wave per body, once literals of
-  // 65..896 bytes ran inside the group (6.60-6.63 while each was a
-  // wave-wide copy with a window restart).
-  const i64 pack_opt = opt(kOptExecPack);
-  const u32 kPackBatch = pack_opt >= 1 && pack_opt <= 64 ? (u32)pack_opt : 0u;
-  auto launch_packed = [&](hipStream_t st) -> hipError_t {
-    const u32 grid = kSmallPersist && kSmallPersist < small_blocks ? kSmallPersist : small_blocks;
-    exec_packed_kernel<<<grid, kWavesPerBlock * 64, 0, st>>>(
-        in, in_off, in_len, out, out_off, out_len, status, bm_base, bitmap, walk_perm, walk_hist, kSplitClass,
-        reinterpret_cast<u32*>(w + kWsPackNext), kPackBatch, keep_hist);
-    return hipGetLastError();
-  };
-  SideStream* side = fork ? side_stream() : nullptr;
+
+  // ---- streams
+  SideStream* side = p.fork ? side_stream() : nullptr;
   if (side) {
-    // the plan pass lists the large messages; pass 1b starts on them while
-    // the lane walk runs
-    index_plan_kernel<<<(n_msgs + kPlanThreads - 1) / kPlanThreads, kPlanThreads, 0, stream>>>(
-        in, in_off, in_len, n_msgs, out_cap, out_len, status, flags, counter, bm_base, bitmap,
-        cap_words, big_count, big_list, big_threshold, kWalkOrder ? walk_rank : nullptr, walk_hist);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (kWalkOrder) {
-      walk_offsets_kernel<<<1, 64, 0, stream>>>(walk_hist);
-      walk_scatter_kernel<<<(n_msgs + 255) / 256, 256, 0, stream>>>(in_len, n_msgs, status, walk_rank,
-                                                                  walk_hist, walk_perm);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    // The huge messages (> kHugeIndexBytes compressed) are walked and
-    // executed on a second side stream, so the other large messages'
-    // execution starts when their own (shorter) walks end instead of after
-    // the longest walk: CM 7.6 -> see DESIGN.md section 5.
-    std::lock_guard<std::mutex> lk(side->mu);
-    if ((e = hipEventRecord(side->fork, stream)) != hipSuccess) return e;
-    if ((e = hipStreamWaitEvent(side->stream, side->fork, 0)) != hipSuccess) return e;
-    const bool split = kSplitHuge && side->stream2;
-    if (split) {
-      if ((e = hipStreamWaitEvent(side->stream2, side->fork, 0)) != hipSuccess) return e;
-      if ((e = chunked ? launch_big_chunked(side->stream2, set1) : launch_big(side->stream2, set1, 1u)) != hipSuccess)
-        return e;
-      if ((e = hipEventRecord(side->join2, side->stream2)) != hipSuccess) return e;
-    }
-    if ((e = launch_big(side->stream, set0, split ? 2u : 0u)) != hipSuccess) return e;
-    if ((e = hipEventRecord(side->join, side->stream)) != hipSuccess) return e;
-    const bool three = split_walk && kWalkOrder && side->stream3;
-    if (three) {
-      // the larger small bodies: walk and execution on the third stream
-      if ((e = hipStreamWaitEvent(side->stream3, side->fork, 0)) != hipSuccess) return e;
-      if ((e = launch_index(true, side->stream3, 1u)) != hipSuccess) return e;
-      if ((e = launch_small(side->stream3, 1u)) != hipSuccess) return e;
-      if ((e = hipEventRecord(side->join3, side->stream3)) != hipSuccess) return e;
-      if ((e = launch_index(true, stream, 2u)) != hipSuccess) return e;
-      if ((e = launch_small(stream, 2u)) != hipSuccess) return e;
-      if ((e = hipStreamWaitEvent(stream, side->join3, 0)) != hipSuccess) return e;
-    } else {
-      if ((e = launch_index(true)) != hipSuccess) return e;
-      if (kWalkOrder && split_mode == 2) {
-        if ((e = launch_small(stream, 3u)) != hipSuccess) return e;
-      } else if (kWalkOrder && split_mode == 3) {
-        if ((e = kPackBatch ? launch_packed(stream) : launch_small(stream, 2u)) != hipSuccess) return e;
-        if ((e = launch_small(stream, 1u)) != hipSuccess) return e;
-      } else {
-        if ((e = launch_small(stream, 0u)) != hipSuccess) return e;
-      }
-    }
-    if ((e = hipStreamWaitEvent(stream, side->join, 0)) != hipSuccess) return e;
-    if (split && (e = hipStreamWaitEvent(stream, side->join2, 0)) != hipSuccess) return e;
+    if ((e = launch_forked(p, b, side, stream)) != hipSuccess) return e;
   } else {
     // one stream: pass 1, pass 1b, then one exec launch whose first blocks
     // take the large messages (dispatched first) and the rest one message
     // per wave
-    if ((e = launch_index(false)) != hipSuccess) return e;
-    if ((e = launch_index_big(stream)) != hipSuccess) return e;
+    if ((e = launch_index(p, b, false, s1)) != hipSuccess) return e;
+    if ((e = launch_index_big(p, b, s1, b.set0, 0u)) != hipSuccess) return e;
     if (two) {
       std::lock_guard<std::mutex> lk(two->mu);
-      if ((e = hipEventRecord(two->pass1, stream)) != hipSuccess) return e;
-      if ((e = hipStreamWaitEvent(caller_stream, two->pass1, 0)) != hipSuccess) return e;
-      stream = caller_stream;
+      if ((e = hipEventRecord(two->pass1, s1)) != hipSuccess) return e;
+      if ((e = hipStreamWaitEvent(stream, two->pass1, 0)) != hipSuccess) return e;
     }
-    ek<<<big_blocks + small_blocks, kWavesPerBlock * 64, 0, stream>>>(
-        in, in_off, in_len, n_msgs, out, out_off, out_len, status, bm_base, bitmap,
-        reinterpret_cast<const u32*>(seg_list), set0.seg_count, whole_list, set0.whole_count, set0.exec_next,
-        big_blocks, big_threshold, kPrio, keep_hist, 0u, nullptr, nullptr, 0u, 0u);
+    b.ek<<<p.big_blocks + p.small_blocks, kWavesPerBlock * 64, 0, stream>>>(
+        in, in_off, in_len, n_msgs, out, out_off, out_len, status, b.bm_base, b.bitmap,
+        reinterpret_cast<const u32*>(b.set0.seg_list), b.set0.seg_count, b.set0.whole_list, b.set0.whole_count,
+        b.set0.exec_next, p.big_blocks, p.big_threshold, p.prio, p.keep_hist, 0u, nullptr, nullptr, 0u, 0u);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  fallback_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off,
-                                                         out_len, status, flags, bm_base, cap_words,
-                                                         reinterpret_cast<u32*>(w + kWsFallbackCount));
+  fallback_kernel<<<p.fallback_grid, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_len, status,
+                                                      flags, b.bm_base, p.cap_words, b.ctr(kWsFallbackCount));
   return hipGetLastError();
 }
 

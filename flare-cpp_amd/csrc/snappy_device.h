@@ -130,33 +130,7 @@ __host__ __device__ __forceinline__ u32 split_region(u32 total, u32 hdr, u32 nfr
   return stride;
 }
 
-// ---- path report (capi.hip: fsg_decompress_report and its kin): what each
-// codec's 256-byte workspace header holds after a call, read from a host copy
-struct DecodeHeaderCounts {
-  u32 bitmap_words;  // the bump allocator's final value
-  u32 large, huge;   // messages listed for the wave-per-message index pass
-  u32 fallback, fallback_bitmap, fallback_wide, fallback_guard;  // pass 3 and its causes
-};
-struct EncodeHeaderCounts {
-  u32 units, split, fallback;
-  u64 unit_bytes;
-};
-u64 decode_v4_bitmap_capacity_words(u32 n_msgs, size_t ws_bytes);
-void decode_v4_header_counts(const void* header, DecodeHeaderCounts* c);
-void encode_v3_header_counts(const void* header, EncodeHeaderCounts* c);
-u32 encode_v3_wave_min(u32 n_msgs, u32 max_in_len, size_t ws_bytes, size_t tables_bytes, u32 wave_min,
-                       bool* planned);
-void encode_v3_wave_split(u32* share_permille, u64* all_bytes);
-u64 lz4_decode_bitmap_capacity_words(u32 n_msgs, size_t ws_bytes);
-void lz4_decode_header_counts(const void* header, DecodeHeaderCounts* c);
-// LZ4 compress (lz4_encode_wave.hip): bodies of at least wave_min bytes go to
-// the wave encoder; kLz4WaveNone = none do
-constexpr u64 kLz4WaveNone = 1ull << 32;
-struct Lz4EncodeHeaderCounts {
-  u32 listed, wave_messages;
-  u64 wave_bytes;
-};
-size_t lz4_compress_tables_bytes(u32 n_msgs);  // the lanes' tables alone: the workspace before the wave encoder
-void lz4_encode_header_counts(const void* header, Lz4EncodeHeaderCounts* c);
+// (The host entry points -- launch_*, workspace sizes, the path report's
+// header counts -- are declared in launch.h.)
 
 }  // namespace fsg

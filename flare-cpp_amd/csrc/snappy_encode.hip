@@ -17,6 +17,7 @@
 //   * FindMatchLength (snappy-internal.h:87-121) compares 64 bytes per step,
 //     one per lane, the first mismatch found by ballot;
 //   * literals are copied by all lanes 16 bytes at a time.
+#include "launch.h"
 #include "snappy_device.h"
 
 namespace fsg {

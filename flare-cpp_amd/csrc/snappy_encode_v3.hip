@@ -33,6 +33,7 @@
 //
 // Output bytes equal snappy::Compress(Source*, Sink*) (snappy.cc:875-954);
 // EmitLiteral / EmitCopy follow snappy.cc:156-232.
+#include "launch.h"
 #include "options.h"
 #include "snappy_device.h"
 
