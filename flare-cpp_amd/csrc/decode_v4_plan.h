@@ -1,4 +1,5 @@
-// decode_v4_plan.h -- two-pass Snappy decode (snappy_decode_v4.hip): the
+// decode_v4_plan.h -- two-pass Snappy decode (snappy_decode_v4.hip and the
+// decode_v4_*.h of its passes): the
 // workspace layout and everything launch_decode_v4 decides before its first
 // launch, as plain host arithmetic.  No HIP include: tests/cpp/
 // test_decode_plan.cc checks it on the CPU.  DESIGN.md section 4, "Decode".
@@ -35,18 +36,19 @@ static_assert(kIdxWaves == 1 || kIdxWaves == 2 || kIdxWaves == 4, "tag table ini
 #endif
 constexpr u32 kIdxWavesSerial = FSG_IDX_WAVES_SERIAL;
 static_assert(kIdxWavesSerial == 1 || kIdxWavesSerial == 2 || kIdxWavesSerial == 4, "tag table init");
-// Size classes of the planned lane walk (see index_plan_kernel).
+// Size classes of the planned lane walk (see index_plan_kernel,
+// decode_v4_index.h).
 constexpr u32 kWalkClasses = 16;
 constexpr u32 kPlanThreads = 1024;
 
-// ---- pass 1b (index_big_message, run by exec_kernel's large-message waves) geometry
+// ---- pass 1b (index_big_message, decode_v4_index_big.h) geometry
 constexpr u32 kBigIndexMin = 8 * 1024;       // large: compressed size above
 constexpr u32 kBigIndexMax = 48 * 1024;      // clamp(4 x the batch mean, min, max)
 #ifndef FSG_HUGE_KB
 #define FSG_HUGE_KB 256
 #endif
 constexpr u32 kHugeIndexBytes = FSG_HUGE_KB * 1024;  // large ones handed out first (forked: chunked walk)
-// chunked pass 1b (chunk_*_kernel)
+// chunked pass 1b (chunk_*_kernel, decode_v4_chunked.h)
 constexpr u32 kChunkBytes = 32 * 1024;  // a multiple of 512: chunks own whole bitmap words
 struct ChunkRec {
   u32 m, k, exit, bad, len, base, flags, nchunks;
@@ -69,8 +71,9 @@ constexpr u32 kSingleLiteral = 0x80000000u;
 constexpr u32 kWindow = FSG_WINDOW;  // LDS output window per wave
 constexpr u32 kKeep = FSG_KEEP;      // history kept when the window slides
 // After a slide op - sbase <= keep + 15; a group adds <= 16 * kMaxPieces
-// bytes and an OR store writes up to 20 bytes past a piece's start, all of
-// which must stay inside the window's kWindow + 32 bytes.
+// (decode_v4_exec_common.h) bytes and an OR store writes up to 20 bytes past
+// a piece's start, all of which must stay inside the window's kWindow + 32
+// bytes.
 constexpr u32 kMaxKeep = (kWindow - 16 * 64 - 48) & ~15u;
 static_assert(kKeep <= kMaxKeep, "kept history leaves room for one group");
 // Path report: the packed pass counts the bodies it hands to pass 3 in the
@@ -384,7 +387,8 @@ inline DecodePlan decode_v4_plan(u32 n_msgs, size_t ws_bytes, bool two_stream, c
   const u32 small_persist = sp_opt >= 0 && sp_opt <= (1 << 20) ? (u32)sp_opt : 3584u;
   p.small_grid = small_persist && small_persist < small_blocks ? small_persist : small_blocks;
   p.small_stride = p.small_grid < small_blocks ? p.small_grid : 0u;
-  // The short bodies of walk part 2 packed several to a wave (exec5_packed):
+  // The short bodies of walk part 2 packed several to a wave (exec5_packed,
+  // decode_v4_packed.h):
   // option exec_pack = bodies per batch (1..64, default 32; 0 = one wave per
   // body, the small-message grid above).  Grid: the small-message grid's
   // size.  Measured on CM (A/B on one box):

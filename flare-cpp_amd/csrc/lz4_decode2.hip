@@ -1,6 +1,6 @@
 // lz4_decode2.hip -- two-pass LZ4 block decode for gfx950 (SURVEY.md section
 // 8(f) row 4: COMPRESS_TYPE_LZ4, /root/reference/flare/rpc/options.proto:74),
-// on the machinery of the Snappy decoder (snappy_decode_v4.hip): a
+// on the machinery of the Snappy decoder (snappy_decode_v4.hip, wave_util.h): a
 // lane-per-message index pass that validates every block and marks its
 // sequence boundaries in a bitmap, then a wave-per-message execution pass.
 //
@@ -121,12 +121,8 @@ __device__ unsigned long long g_l4_stamps[8];
 #define L4COUNT(k) do { } while (0)
 #endif
 
-// Far chunks: earlier output of this wave, read through the slot's buffer
-// with an sc1 load (served by L2; the CU's L1 may hold a line filled before
-// the bytes were stored -- see snappy_decode_v4.hip, far_load).
-__device__ __forceinline__ u32x4 far16(__amdgpu_buffer_rsrc_t r, u32 off) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 16);
-}
+// (Far chunks, earlier output of this wave, are read through the slot's
+// buffer with wave_util.h's far_load.)
 
 // ===========================================================================
 // Pass 1: validate + index, one lane per message.
@@ -429,7 +425,7 @@ __global__ __launch_bounds__(64) void lz4_index_kernel(
 // input through a 256-byte per-lane ring loaded 128 bytes per iteration, and a
 // lone lane takes ~60 ms per MB.  Here the wave stages the block into an 8 KiB
 // LDS ring, 4 KiB (64 lanes x 64 bytes) at a time, and indexes it 64 bytes
-// per step, as the Snappy pass 1b (snappy_decode_v4.hip, index_big_message):
+// per step, as the Snappy pass 1b (decode_v4_index_big.h, index_big_message):
 // every lane decodes the sequence that would start at its byte (literal
 // length, offset field, match length, successor, the checks that need no walk
 // state), the real sequence starts in the window -- the chain from the
@@ -862,7 +858,7 @@ __device__ __forceinline__ void lz4_exec_message(
           for (u32 k0 = 0; k0 < ML; k0 += 4096) {
             u32x4 x[4];
 #pragma unroll
-            for (u32 r = 0; r < 4; ++r) x[r] = far16(orsrc, src + k0 + 1024 * r + lane * 16 + obal);
+            for (u32 r = 0; r < 4; ++r) x[r] = far_load(orsrc, src + k0 + 1024 * r + lane * 16 + obal);
 #pragma unroll
             for (u32 r = 0; r < 4; ++r) {
               const u32 k = k0 + 1024 * r + lane * 16;
@@ -870,14 +866,14 @@ __device__ __forceinline__ void lz4_exec_message(
             }
           }
         } else if (OFF < 16) {  // period < 16: every piece is the same expanded pattern
-          const u32x4 P = expand_pattern(far16(orsrc, src + obal), OFF, sel_tab);
+          const u32x4 P = expand_pattern(far_load(orsrc, src + obal), OFF, sel_tab);
           const u32 stp = pat_step(OFF);
           for (u32 k = lane * stp; k < ML; k += 64 * stp) store_exact(ob + d + k, P, ML - k < stp ? ML - k : stp);
         } else if (OFF <= kL4StageMax) {
           // period OFF staged twice in the window (free until the restart
           // below): chunk j reads its 16 bytes at phase 16 j mod OFF
           for (u32 i = 16 * lane; i < OFF; i += 1024) {
-            const u32x4 x = far16(orsrc, src + i + obal);
+            const u32x4 x = far_load(orsrc, src + i + obal);
             const u32 c = OFF - i < 16 ? OFF - i : 16u;
             store_exact(sb + i, x, c);
             store_exact(sb + OFF + i, x, c);
@@ -898,7 +894,7 @@ __device__ __forceinline__ void lz4_exec_message(
           for (u32 k0 = 0; k0 < ML; k0 += step) {
             const u32 e = k0 + step < ML ? k0 + step : ML;
             for (u32 k = k0 + 16 * lane; k < e; k += 1024)
-              store_exact(ob + d + k, far16(orsrc, src + k + obal), e - k < 16 ? e - k : 16u);
+              store_exact(ob + d + k, far_load(orsrc, src + k + obal), e - k < 16 ? e - k : 16u);
             wait_all_memory();
           }
         }
@@ -915,7 +911,7 @@ __device__ __forceinline__ void lz4_exec_message(
         const int lo = sbase + 16 * (int)lane;
         if (lo >= 0 && (u32)lo < op) {
           const u32 c = op - (u32)lo < 16 ? op - (u32)lo : 16u;
-          store_exact(sb + 16 * lane, far16(orsrc, (u32)lo + obal), c);
+          store_exact(sb + 16 * lane, far_load(orsrc, (u32)lo + obal), c);
         }
       }
       wave_lds_fence();
@@ -1028,7 +1024,7 @@ __device__ __forceinline__ void lz4_exec_message(
           xs[r] = __builtin_amdgcn_raw_buffer_load_b128(irsrc, a, 0, 0);
           ys[r] = __builtin_amdgcn_raw_buffer_load_b32(irsrc, a + 16, 0, 0);
         } else if (it < nit) {
-          xs[r] = far16(orsrc, mo + 16 * (it - nlm) + obal);
+          xs[r] = far_load(orsrc, mo + 16 * (it - nlm) + obal);
         }
       }
       if (i0 == 0) {  // while the loads are in flight
@@ -1076,12 +1072,7 @@ __device__ __forceinline__ void lz4_exec_message(
         u32x4 x = lds_read16(sb + sw);
         if (pf) x = expand_pattern(x, off, sel_tab);
         const u32x4 o = lds_read16(sb + cw);
-        const u32x4 mk = mtab[nb];
-        u32x4 y;
-        y[0] = (x[0] & mk[0]) | (o[0] & ~mk[0]);
-        y[1] = (x[1] & mk[1]) | (o[1] & ~mk[1]);
-        y[2] = (x[2] & mk[2]) | (o[2] & ~mk[2]);
-        y[3] = (x[3] & mk[3]) | (o[3] & ~mk[3]);
+        const u32x4 y = merge16(x, o, mtab[nb]);
         __builtin_memcpy(sb + cw, &y, 16);
         rem -= nb;
         cw += nb;

@@ -12,7 +12,7 @@
 namespace fsg {
 
 enum Opt : int {
-  // Snappy two-pass decode (snappy_decode_v4.hip; read once per call into DecodeOpts and range-checked in decode_v4_plan.h)
+  // Snappy two-pass decode (snappy_decode_v4.hip, read_decode_opts; read once per call into DecodeOpts and range-checked in decode_v4_plan.h)
   kOptDecodeFork,         // -1 automatic (> 128K messages), 0 one stream, 1 forked path
   kOptSplitWalk,          // forked small-message execution order 0..3 (3 default)
   kOptSplitClass,         // walk class split point of mode 3

@@ -2,7 +2,7 @@
 // lane (/root/reference/flare/io/snappy/snappy.cc:716-787 with the writer
 // checks of :1141-1227 / :1331-1481).  Used by the lane-per-message kernel
 // (snappy_decode.hip) and by the two-pass decoder's fallback pass for the
-// messages whose tag bitmap did not fit the workspace (snappy_decode_v4.hip).
+// messages whose tag bitmap did not fit the workspace (snappy_decode_v4.hip, fallback_kernel).
 #pragma once
 
 #include "snappy_device.h"

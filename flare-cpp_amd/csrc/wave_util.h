@@ -1,7 +1,8 @@
 // wave_util.h -- wave-level helpers shared by the gfx950 two-pass decoders
-// (Snappy: snappy_decode_v4.hip; LZ4: lz4_decode2.hip): DPP scans, buffer
-// loads of a message's bytes, LDS ordering, the OR store into a zeroed
-// output window.
+// (Snappy: snappy_decode_v4.hip and its decode_v4_*.h; LZ4: lz4_decode2.hip):
+// DPP scans, buffer loads of a message's bytes and of a wave's own earlier
+// output, LDS ordering, the OR store and the masked merge into the output
+// window.
 #pragma once
 
 #include "snappy_pieces.h"
@@ -52,14 +53,19 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t msg_rsrc(const u8* abase, u32 
                                            (int)((bytes + 3) & ~3u), 0x00020000);
 }
 
+// The 20 bytes (d, d4) shifted down by t (0..3) bytes: bytes t .. t+15.
+__device__ __forceinline__ u32x4 shift16(const u32x4& d, u32 d4, u32 t) {
+  return u32x4{__builtin_amdgcn_alignbyte(d[1], d[0], t), __builtin_amdgcn_alignbyte(d[2], d[1], t),
+               __builtin_amdgcn_alignbyte(d[3], d[2], t), __builtin_amdgcn_alignbyte(d4, d[3], t)};
+}
+
 // 16 bytes at buffer offset P (any alignment): one 16-byte and one 4-byte
 // load at the dword below P, then a byte shift (bytes past the end read 0).
 __device__ __forceinline__ u32x4 rsrc_load16(__amdgpu_buffer_rsrc_t r, u32 P) {
   const u32 a = P & ~3u, s = P & 3u;
   const u32x4 d = __builtin_amdgcn_raw_buffer_load_b128(r, a, 0, 0);
   const u32 d4 = __builtin_amdgcn_raw_buffer_load_b32(r, a + 16, 0, 0);
-  return u32x4{__builtin_amdgcn_alignbyte(d[1], d[0], s), __builtin_amdgcn_alignbyte(d[2], d[1], s),
-               __builtin_amdgcn_alignbyte(d[3], d[2], s), __builtin_amdgcn_alignbyte(d4, d[3], s)};
+  return shift16(d, d4, s);
 }
 
 // The same in two steps, so that several loads are in flight before the
@@ -74,9 +80,22 @@ __device__ __forceinline__ Raw16 raw_load16(__amdgpu_buffer_rsrc_t r, u32 P) {
   return Raw16{__builtin_amdgcn_raw_buffer_load_b128(r, a, 0, 0),
                __builtin_amdgcn_raw_buffer_load_b32(r, a + 16, 0, 0), P & 3u};
 }
-__device__ __forceinline__ u32x4 shifted16(const Raw16& x) {
-  return u32x4{__builtin_amdgcn_alignbyte(x.d[1], x.d[0], x.s), __builtin_amdgcn_alignbyte(x.d[2], x.d[1], x.s),
-               __builtin_amdgcn_alignbyte(x.d[3], x.d[2], x.s), __builtin_amdgcn_alignbyte(x.d4, x.d[3], x.s)};
+__device__ __forceinline__ u32x4 shifted16(const Raw16& x) { return shift16(x.d, x.d4, x.s); }
+
+// A far copy's 16 source bytes: output this wave stored in an earlier group,
+// read from the slot with an sc1 load, which is served by L2 and bypasses
+// this CU's L1 (MI355X_MICROARCH.md, visibility table).  Why that matters:
+// an L1 line can be filled while part of it is still unwritten -- a far load
+// just after a long literal's window restart, or the neighbouring message's
+// slot sharing a 128-byte line -- and the vector L1 is not specified to pick
+// up later stores.  Ordering in L2: a wave's vector memory operations return
+// in issue order, loads and stores alike, and every far source was flushed
+// at least one group before it is read, behind that group's waited tag loads
+// ("far copies").  src + 16 <= op <= the slot length
+// (far sources end >= 16 bytes below the window base, which is <= op - 16), so
+// the range check never clips a needed byte.
+__device__ __forceinline__ u32x4 far_load(__amdgpu_buffer_rsrc_t r, u32 off) {
+  return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 16);
 }
 
 // The 5 tag bytes at buffer offset P: bytes P..P+3 in .x, byte P+4 in the low
@@ -110,6 +129,13 @@ __device__ __forceinline__ u32x4 lds_read16(const u8* p) {
   u32x4 v;
   __builtin_memcpy(&v, p, 16);
   return v;
+}
+
+// Rounds B's exact write: x where the byte mask mk (mtab[n]) is set, the
+// window's own bytes o elsewhere (one v_bfi per dword).
+__device__ __forceinline__ u32x4 merge16(const u32x4& x, const u32x4& o, const u32x4& mk) {
+  return u32x4{(x[0] & mk[0]) | (o[0] & ~mk[0]), (x[1] & mk[1]) | (o[1] & ~mk[1]),
+               (x[2] & mk[2]) | (o[2] & ~mk[2]), (x[3] & mk[3]) | (o[3] & ~mk[3])};
 }
 
 // OR n (1..16) bytes of v into the window at byte offset w, whose bytes

@@ -89,9 +89,12 @@ def test_option_calls():
 
 def test_decode_launch_reads_no_environment():
     """The drop-in's launch paths take their knobs from the option table:
-    no getenv in the HIP sources outside capi.hip's load-time read."""
+    no getenv in the HIP sources or the headers they include outside
+    capi.hip's load-time read."""
     src = Path(__file__).resolve().parents[1] / "flare-cpp_amd" / "csrc"
-    for f in src.glob("*.hip"):
+    files = sorted(src.glob("*.hip")) + sorted(src.glob("*.h"))
+    assert any(f.name == "capi.hip" for f in files) and any(f.suffix == ".h" for f in files)
+    for f in files:
         text = f.read_text()
         if f.name == "capi.hip":
             assert text.count("getenv(") == 2  # env_int (kernel variants) + the option table's one-time read

@@ -1,4 +1,4 @@
-"""The packed execution pass's virtual layout (csrc/snappy_decode_v4.hip,
+"""The packed execution pass's virtual layout (csrc/decode_v4_packed.h,
 exec5_packed), restated on the host: the bodies of a batch end to end, body
 j at V_j congruent to its slot address modulo 16, so that every 16-byte
 virtual block belongs to one body and maps to one 16-byte-aligned slot

@@ -1,6 +1,7 @@
 """Streams whose copy sources sit exactly at the edge of pass 2's LDS window.
 
-exec_message (flare-cpp_amd/csrc/snappy_decode_v4.hip, pass 2) assembles a
+Pass 2 (exec5_message, flare-cpp_amd/csrc/decode_v4_exec5.h; variant 4:
+exec_message, decode_v4_exec4.h) assembles a
 message's output in a per-wave window holding output positions
 [sbase, sbase + 3072).  A copy whose source starts below sbase is a "far" copy:
 round A loads it from the output already stored to global memory; any other

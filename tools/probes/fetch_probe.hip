@@ -10,7 +10,7 @@
 //   rand_off   as rand_line, at a random 16-B-aligned offset in the line
 //   rand_any   16 B at a random byte offset (a load may span two lines)
 //   far_*      the exec pass's far-copy load itself: a 16-B buffer load with
-//              sc1 (far_load, csrc/snappy_decode_v4.hip) at a random byte
+//              sc1 (far_load, csrc/wave_util.h) at a random byte
 //              offset, 2^24 loads, from a buffer left resident by a warm-up
 //              kernel that every XCD runs over the whole buffer:
 //              far_l2 (1 MiB: resident in every XCD's 4 MB L2), far_mall
