@@ -51,6 +51,8 @@ constexpr OptDesc kOptDesc[fsg::kOptCount] = {
     {"lz4_big_min", "FSG_L4_BIG_MIN", -1},
     {"lz4_encode_wave_min", "FSG_L4_ENC_WAVE_MIN", -1},
     {"lz4_encode_wave_per_cu", "FSG_L4_ENC_WAVE_PER_CU", 0},
+    {"lz4f_force_serial", "FSG_L4F_FORCE_SERIAL", 0},
+    {"lz4f_block_wave_min", "FSG_L4F_BLOCK_WAVE_MIN", -1},
 };
 // DecodeOpts' initialisers (decode_v4_plan.h, which the CPU test of the launch
 // plan uses as "the defaults") are this table's
@@ -265,6 +267,13 @@ int lz4_encode_path(size_t workspace_bytes, uint32_t n_msgs, fsg::u64* wave_min)
   const int64_t v = fsg::opt(fsg::kOptLz4EncodeWaveMin);
   *wave_min = v < 0 ? lz4_encode_wave_min_auto(n_msgs) : v >= 0xFFFFFFFFll ? fsg::kLz4WaveNone : (fsg::u64)v;
   return 0;
+}
+// fsg_lz4f_compress_batch: the block encode's threshold, from option
+// lz4f_block_wave_min by the rule of lz4_encode_path; the automatic rule sees
+// the block entries of the workspace as its batch
+fsg::u64 lz4f_block_wave_min(uint32_t block_entries) {
+  const int64_t v = fsg::opt(fsg::kOptLz4fBlockWaveMin);
+  return v < 0 ? lz4_encode_wave_min_auto(block_entries) : v >= 0xFFFFFFFFll ? fsg::kLz4WaveNone : (fsg::u64)v;
 }
 }  // namespace
 
@@ -572,6 +581,98 @@ int fsg_lz4_decompress_batch_2s(const uint8_t* d_in, const uint64_t* d_in_off, c
                                         d_status, d_workspace, workspace_bytes, (hipStream_t)stream,
                                         (hipStream_t)pass1_stream),
                 "fsg_lz4_decompress_batch_2s");
+}
+
+// ---- LZ4 frames (include/flare_lz4_gpu.h, "LZ4 frames")
+size_t fsg_lz4f_max_frame_length(size_t n, uint32_t block_size_id) {
+  if (block_size_id < 4 || block_size_id > 7) return 0;
+  const size_t bs = (size_t)1 << (8 + 2 * block_size_id);
+  return 15 + 4 * ((n + bs - 1) / bs) + n + 4 + 4;
+}
+
+size_t fsg_lz4f_compress_workspace_bytes(uint32_t n_msgs, uint64_t total_in_bytes, uint32_t block_size_id) {
+  if (block_size_id < 4 || block_size_id > 7) return 0;
+  return fsg::lz4f_compress_workspace_bytes(n_msgs, total_in_bytes, block_size_id);
+}
+
+int fsg_lz4f_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                            uint32_t n_msgs, uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len,
+                            int32_t* d_status, uint32_t block_size_id, uint32_t flags, void* d_workspace,
+                            size_t workspace_bytes, void* stream) {
+  if (block_size_id < 4 || block_size_id > 7 || (flags & ~1u)) return FSG_ERR_INVALID_ARG;
+  if (n_msgs == 0) return FSG_SUCCESS;
+  if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len || !d_status || !d_workspace)
+    return FSG_ERR_INVALID_ARG;
+  const fsg::u32 entries = fsg::lz4f_compress_block_capacity(n_msgs, workspace_bytes, block_size_id);
+  if (entries == 0) return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_lz4f_encode(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_len, d_status,
+                                        block_size_id, flags, d_workspace, workspace_bytes,
+                                        lz4f_block_wave_min(entries), (hipStream_t)stream),
+                "fsg_lz4f_compress_batch");
+}
+
+size_t fsg_lz4f_decompress_workspace_bytes(uint32_t n_msgs, uint64_t total_in_bytes) {
+  return fsg::lz4f_decompress_workspace_bytes(n_msgs, total_in_bytes);
+}
+
+int fsg_lz4f_decompress_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                              uint32_t n_msgs, uint8_t* d_out, const uint64_t* d_out_off,
+                              const uint32_t* d_out_cap, uint32_t* d_out_len, int32_t* d_status,
+                              void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (n_msgs == 0) return FSG_SUCCESS;
+  if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status ||
+      !d_workspace || fsg::lz4f_decompress_block_capacity(n_msgs, workspace_bytes) == 0)
+    return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_lz4f_decode(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
+                                        d_status, d_workspace, workspace_bytes,
+                                        fsg::opt(fsg::kOptLz4fForceSerial) != 0, (hipStream_t)stream),
+                "fsg_lz4f_decompress_batch");
+}
+
+int fsg_lz4f_content_sizes_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                 uint32_t n_msgs, uint64_t* d_content_size, int32_t* d_status, void* stream) {
+  if (n_msgs && (!d_in || !d_in_off || !d_in_len || !d_content_size || !d_status)) return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_lz4f_content_sizes(d_in, d_in_off, d_in_len, n_msgs, d_content_size, d_status,
+                                               (hipStream_t)stream),
+                "fsg_lz4f_content_sizes_batch");
+}
+
+int fsg_lz4f_compress_report(const void* header_host_copy, uint32_t n_msgs, size_t workspace_bytes,
+                             uint32_t block_size_id, struct fsg_lz4f_encode_report* out) {
+  if (!out || block_size_id < 4 || block_size_id > 7) return FSG_ERR_INVALID_ARG;
+  *out = fsg_lz4f_encode_report{};
+  if (n_msgs == 0) return FSG_SUCCESS;
+  out->block_entries = fsg::lz4f_compress_block_capacity(n_msgs, workspace_bytes, block_size_id);
+  if (out->block_entries == 0 || !header_host_copy) return FSG_ERR_INVALID_ARG;
+  const fsg::u64 wave_min = lz4f_block_wave_min((uint32_t)out->block_entries);
+  out->block_wave_min = wave_min < 0xFFFFFFFFull ? wave_min : 0xFFFFFFFFull;
+  fsg::Lz4fEncodeHeaderCounts c;
+  fsg::lz4f_encode_header_counts(header_host_copy, &c);
+  out->blocks = c.blocks;
+  out->raw_blocks = c.raw_blocks;
+  out->overflow_messages = c.overflow_messages;
+  return FSG_SUCCESS;
+}
+
+int fsg_lz4f_decompress_report(const void* header_host_copy, uint32_t n_msgs, size_t workspace_bytes,
+                               struct fsg_lz4f_decode_report* out) {
+  if (!out) return FSG_ERR_INVALID_ARG;
+  *out = fsg_lz4f_decode_report{};
+  if (n_msgs == 0) return FSG_SUCCESS;
+  out->block_entries = fsg::lz4f_decompress_block_capacity(n_msgs, workspace_bytes);
+  if (out->block_entries == 0 || !header_host_copy) return FSG_ERR_INVALID_ARG;
+  fsg::Lz4fDecodeHeaderCounts c;
+  fsg::lz4f_decode_header_counts(header_host_copy, &c);
+  out->fast_messages = c.fast_messages;
+  out->fast_blocks = c.fast_blocks;
+  out->empty_messages = c.empty_messages;
+  out->serial_linked = c.serial_linked;
+  out->serial_no_size = c.serial_no_size;
+  out->serial_rejected = c.serial_rejected;
+  out->serial_forced = c.serial_forced;
+  out->checksummed_units = c.checksummed_units;
+  out->inner_fallback_blocks = c.inner_fallback;
+  return FSG_SUCCESS;
 }
 
 }  // extern "C"

@@ -79,6 +79,22 @@ hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len
                               const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
                               size_t ws_bytes, hipStream_t stream, hipStream_t pass1_stream);
 
+// ---- LZ4 frames (lz4_frame.hip; include/flare_lz4_gpu.h, "LZ4 frames").  The
+// calls get no input size: the workspace says what it was sized for, and the
+// *_block_capacity functions give the block entries it holds (0: too small).
+size_t lz4f_compress_workspace_bytes(u32 n_msgs, u64 total_in_bytes, u32 block_size_id);
+size_t lz4f_decompress_workspace_bytes(u32 n_msgs, u64 total_in_bytes);
+u32 lz4f_compress_block_capacity(u32 n_msgs, size_t ws_bytes, u32 block_size_id);
+u32 lz4f_decompress_block_capacity(u32 n_msgs, size_t ws_bytes);
+hipError_t launch_lz4f_encode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
+                              const u64* out_off, u32* out_len, i32* status, u32 block_size_id, u32 flags, void* ws,
+                              size_t ws_bytes, u64 wave_min, hipStream_t stream);
+hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
+                              const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
+                              size_t ws_bytes, bool force_serial, hipStream_t stream);
+hipError_t launch_lz4f_content_sizes(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* sizes,
+                                     i32* status, hipStream_t stream);
+
 // ---- path report (capi.hip: fsg_decompress_report and its kin): what each
 // codec's 256-byte workspace header holds after a call, read from a host copy
 struct DecodeHeaderCounts {
@@ -94,6 +110,16 @@ struct Lz4EncodeHeaderCounts {
   u32 listed, wave_messages;
   u64 wave_bytes;
 };
+struct Lz4fEncodeHeaderCounts {
+  u32 blocks, raw_blocks, overflow_messages;
+};
+struct Lz4fDecodeHeaderCounts {
+  u32 fast_messages, fast_blocks, empty_messages;
+  u32 serial_linked, serial_no_size, serial_rejected, serial_forced;
+  u32 checksummed_units, inner_fallback;
+};
+void lz4f_encode_header_counts(const void* header, Lz4fEncodeHeaderCounts* c);
+void lz4f_decode_header_counts(const void* header, Lz4fDecodeHeaderCounts* c);
 void decode_v4_header_counts(const void* header, DecodeHeaderCounts* c);
 void encode_v3_header_counts(const void* header, EncodeHeaderCounts* c);
 void lz4_decode_header_counts(const void* header, DecodeHeaderCounts* c);

@@ -1,0 +1,647 @@
+// lz4_frame.hip -- LZ4 frame bodies (LZ4 Frame Format 1.6.x, what
+// LZ4F_compressFrame and the lz4 command write) on the batch layout of the
+// block codec: include/flare_lz4_gpu.h, "LZ4 frames".
+//
+// A frame with independent blocks is a list of small LZ4 blocks, so the block
+// codecs this library already has (lz4.hip, lz4_encode_wave.hip,
+// lz4_decode2.hip) run a frame's blocks as if they were messages; the kernels
+// here only cut messages into blocks and put frames together (compress), or
+// take frames apart and judge the result (decompress).  Those launches are
+// called, not changed.
+//
+// Compress: plan (a lane per message: its blocks' columns, staging slots from
+// two counters) -> launch_lz4_encode on the block columns -> XXH32 of the
+// inputs when a content checksum is asked for -> assemble (a wave per message:
+// prefix sum of the stored sizes, size words, block copies, descriptor, end
+// mark).
+// Decompress: index (a lane per message: descriptor, route, the walk over the
+// block size words, block columns) -> stage (a wave per block: varint32 +
+// block bytes into the workspace, a raw block straight to its place) ->
+// launch_lz4_decode2 on the block columns -> verdict (a lane per block: block
+// checksum, status, length) -> finish (a lane per message: content checksum,
+// status; and the serial decoder, lz4_frame_format.h, for linked blocks,
+// frames without a content size and every frame the fast route did not accept).
+#include "launch.h"
+#include "lz4_frame_format.h"
+#include "snappy_device.h"
+
+namespace fsg {
+
+namespace {
+
+// ---- workspace header (the first 256 bytes; u32 indices)
+// compress
+constexpr u32 kFcBlocks = 0;    // blocks asked for (past the capacity when a message did not fit)
+constexpr u32 kFcRaw = 1;       // blocks stored raw
+constexpr u32 kFcOverflow = 2;  // messages whose blocks did not fit the workspace
+constexpr u32 kFcListed = 3;    // blocks of the messages that fitted
+constexpr u32 kFcStage = 4;     // u64: staging bytes asked for
+// decompress
+constexpr u32 kFdBlocks = 0;    // block entries asked for
+constexpr u32 kFdFastMsgs = 1, kFdFastBlocks = 2, kFdEmpty = 3;
+constexpr u32 kFdLinked = 4, kFdNoSize = 5, kFdRejected = 6, kFdForced = 7;
+constexpr u32 kFdSums = 8, kFdInner = 9;
+constexpr u32 kFdStage = 10;    // u64
+constexpr u64 kHead = 256;
+
+// msg_route values
+constexpr u32 kRouteDone = 0, kRouteFast = 1, kRouteLinked = 2, kRouteNoSize = 3, kRouteRejected = 4,
+              kRouteForced = 5;
+// block flags
+constexpr u32 kBlkRaw = 1, kBlkSum = 2, kBlkFailed = 4, kBlkListed = 8;
+
+constexpr u32 kNoFit = 0xFFFFFFFFu;
+
+__host__ __device__ inline u64 round_up(u64 v, u64 a) { return (v + a - 1) / a * a; }
+
+// staging slot of a block of L input bytes in the compressor: the body bound
+// of the block codec (fsg_lz4_max_compressed_length), 16-byte aligned, and 64
+// spare bytes
+__host__ __device__ inline u64 enc_slot(u64 L) { return round_up(5 + L + L / 255 + 16, 16) + 64; }
+// and of a stored block of sz bytes in the decompressor: varint32 + bytes
+__host__ __device__ inline u64 dec_slot(u64 sz) { return round_up(5 + sz, 16) + 16; }
+
+__device__ __forceinline__ u32 wave_scan(u32 v) {
+  const u32 lane = __lane_id();
+#pragma unroll
+  for (u32 d = 1; d < 64; d <<= 1) {
+    const u32 t = __shfl_up(v, d, 64);
+    v += lane >= d ? t : 0u;
+  }
+  return v;
+}
+
+// adds `pred` lanes to a counter: one atomic for the wave's active lanes
+__device__ __forceinline__ void count_lanes(u32* ctr, bool pred) {
+  const u64 b = __ballot(pred);
+  const u64 act = __ballot(true);
+  if (b && __lane_id() == (u32)__builtin_ctzll(act)) atomicAdd(ctr, (u32)__builtin_popcountll(b));
+}
+
+// n bytes from s to d by one wave, exactly: single bytes up to d's 16-byte
+// boundary, 16 bytes per lane, single bytes at the end
+__device__ __forceinline__ void wave_copy(u8* d, const u8* s, u32 n, u32 lane) {
+  u32 head = (16u - (u32)(reinterpret_cast<uintptr_t>(d) & 15)) & 15;
+  if (head > n) head = n;
+  if (lane < head) d[lane] = s[lane];
+  const u32 body = (n - head) & ~15u;
+  for (u32 i = 16 * lane; i < body; i += 1024) copy16(d + head + i, s + head + i);
+  const u32 done = head + body;
+  if (done + lane < n) d[done + lane] = s[done + lane];
+}
+
+struct BlockCols {
+  u64* in_off;   // compress: into d_in; decompress: staged body, into the workspace
+  u64* out_off;  // compress: staging slot, into the workspace; decompress: into d_out
+  u64* src_off;  // decompress: the stored block's bytes, into d_in
+  u32* in_len;
+  u32* out_cap;
+  u32* out_len;
+  i32* status;
+  u32* src_len;  // decompress: stored size
+  u32* flags;
+};
+constexpr u64 kBlockColBytes = 3 * 8 + 6 * 4;
+
+struct MsgCols {
+  u32* route;
+  u32* first;
+  u32* nb;
+  u32* xxh;
+};
+
+// ================================================================ compress
+
+// every block entry: an empty input and a 64-byte slot of its own, so that
+// the entries past the batch's blocks encode to nothing anybody reads
+__global__ __launch_bounds__(256) void lz4f_prefill_kernel(BlockCols c, u32 nb_cap, u64 dummy_off) {
+  const u32 e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= nb_cap) return;
+  c.in_off[e] = 0;
+  c.in_len[e] = 0;
+  c.out_off[e] = dummy_off + 64ull * e;
+}
+
+__global__ __launch_bounds__(64) void lz4f_plan_kernel(const u64* __restrict__ in_off, const u32* __restrict__ in_len,
+                                                     u32 n_msgs, u32 bs, u32* hdr, MsgCols mc, BlockCols c, u32 nb_cap,
+                                                     u64 stage_off, u64 stage_cap) {
+  const u32 m = blockIdx.x * 64 + threadIdx.x;
+  if (m >= n_msgs) return;
+  const u32 n = in_len[m];
+  const u32 nb = (u32)(((u64)n + bs - 1) / bs);
+  mc.nb[m] = nb;
+  mc.first[m] = 0;
+  if (nb == 0) return;
+  const u32 last = n - (nb - 1) * bs;
+  const u64 need = (u64)(nb - 1) * enc_slot(bs) + enc_slot(last);
+  const u32 base = atomicAdd(&hdr[kFcBlocks], nb);
+  u64 sb = atomicAdd(reinterpret_cast<unsigned long long*>(hdr + kFcStage), (unsigned long long)need);
+  if ((u64)base + nb > nb_cap || sb + need > stage_cap) {
+    mc.first[m] = kNoFit;
+    atomicAdd(&hdr[kFcOverflow], 1u);
+    return;
+  }
+  mc.first[m] = base;
+  atomicAdd(&hdr[kFcListed], nb);
+  const u64 io = in_off[m];
+  for (u32 k = 0; k < nb; ++k) {
+    const u32 L = k + 1 < nb ? bs : last;
+    c.in_off[base + k] = io + (u64)k * bs;
+    c.in_len[base + k] = L;
+    c.out_off[base + k] = stage_off + sb;
+    sb += enc_slot(L);
+  }
+}
+
+// XXH32 of each message's bytes, one lane per message
+__global__ __launch_bounds__(64) void lz4f_xxh_kernel(const u8* __restrict__ in, const u64* __restrict__ in_off,
+                                                    const u32* __restrict__ in_len, u32 n_msgs, u32* xxh) {
+  const u32 m = blockIdx.x * 64 + threadIdx.x;
+  if (m >= n_msgs) return;
+  xxh[m] = lz4f::xxh32(in + in_off[m], in_len[m]);
+}
+
+// One wave per message: the frame from the staged blocks.
+__global__ __launch_bounds__(64) void lz4f_assemble_kernel(const u8* __restrict__ in, const u32* __restrict__ in_len,
+                                                         u8* out, const u64* __restrict__ out_off,
+                                                         u32* __restrict__ out_len, i32* __restrict__ status, u32 id,
+                                                         u32 checksum, u32* hdr, MsgCols mc, BlockCols c,
+                                                         const u8* ws) {
+  const u32 m = blockIdx.x;
+  const u32 lane = threadIdx.x;
+  const u32 n = in_len[m];
+  const u32 first = mc.first[m], nb = mc.nb[m];
+  if (first == kNoFit || lz4f::max_frame_length(n, id) > 0xFFFFFFFFull) {
+    if (lane == 0) {
+      out_len[m] = 0;
+      status[m] = kCorrupt;
+    }
+    return;
+  }
+  u8* const ob = out + out_off[m];
+  if (lane == 0) lz4f::write_header(ob, n, id, checksum != 0);
+  u64 pos = n ? 15 : 7;
+  u32 raws = 0;
+  for (u32 k0 = 0; k0 < nb; k0 += 64) {
+    const u32 k = k0 + lane;
+    const bool valid = k < nb;
+    u32 L = 0, stored = 0, hl = 0;
+    bool raw = false;
+    u64 src = 0;
+    if (valid) {
+      const u32 e = first + k;
+      L = c.in_len[e];
+      hl = (u32)varint32_len(L);
+      const u32 csize = c.out_len[e] - hl;
+      raw = csize >= L;
+      stored = raw ? L : csize;
+      src = raw ? c.in_off[e] : c.out_off[e] + hl;
+    }
+    const u32 sz = valid ? 4 + stored : 0;
+    const u32 incl = wave_scan(sz);
+    const u64 at = pos + (incl - sz);
+    if (valid) lz4f::wr32(ob + at, raw ? (L | lz4f::kRawBit) : stored);
+    raws += (u32)__builtin_popcountll(__ballot(valid && raw));
+    const u32 cnt = nb - k0 < 64 ? nb - k0 : 64;
+    for (u32 j = 0; j < cnt; ++j) {
+      const u64 s = __shfl(src, j, 64), a = __shfl(at, j, 64);
+      const u32 len = __shfl(stored, j, 64);
+      const bool r = __shfl((int)raw, j, 64);
+      wave_copy(ob + a + 4, (r ? in : ws) + s, len, lane);
+    }
+    pos += __shfl(incl, 63, 64);
+  }
+  if (lane == 0) {
+    lz4f::wr32(ob + pos, 0);
+    pos += 4;
+    if (checksum) {
+      lz4f::wr32(ob + pos, mc.xxh[m]);
+      pos += 4;
+    }
+    out_len[m] = (u32)pos;
+    status[m] = kOk;
+    if (raws) atomicAdd(&hdr[kFcRaw], raws);
+  }
+}
+
+// ================================================================ decompress
+
+__global__ __launch_bounds__(64) void lz4f_sizes_kernel(const u8* __restrict__ in, const u64* __restrict__ in_off,
+                                                      const u32* __restrict__ in_len, u32 n_msgs, u64* sizes,
+                                                      i32* status) {
+  const u32 m = blockIdx.x * 64 + threadIdx.x;
+  if (m >= n_msgs) return;
+  lz4f::Header h;
+  const i32 st = lz4f::parse_header(in + in_off[m], in_len[m], &h);
+  sizes[m] = h.size;
+  status[m] = st;
+}
+
+// One lane per message: descriptor, route, and for the fast route the walk
+// over the block size words (two walks: sizes, then columns).
+__global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ in, const u64* __restrict__ in_off,
+                                                      const u32* __restrict__ in_len, u32 n_msgs,
+                                                      const u64* __restrict__ out_off, const u32* __restrict__ out_cap,
+                                                      u32* __restrict__ out_len, i32* __restrict__ status, u32* hdr,
+                                                      MsgCols mc, BlockCols c, u32 nb_cap, u64 stage_off,
+                                                      u64 stage_cap, u32 force_serial) {
+  const u32 m = blockIdx.x * 64 + threadIdx.x;
+  if (m >= n_msgs) return;
+  const u8* ib = in + in_off[m];
+  const u64 n = in_len[m];
+  lz4f::Header h;
+  mc.route[m] = kRouteDone;
+  if (lz4f::parse_header(ib, n, &h) != lz4f::kStOk) {
+    out_len[m] = 0;
+    status[m] = kBadHeader;
+    return;
+  }
+  const u64 cap = out_cap[m];
+  if (h.size != lz4f::kNoSize && h.size > cap) {
+    out_len[m] = h.size > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)h.size;
+    status[m] = kSlotTooSmall;
+    return;
+  }
+  // a frame with no blocks is finished here
+  if (n - h.len >= 4 && lz4f::rd32(ib + h.len) == 0) {
+    u32 ol, sums = 0;
+    status[m] = lz4f::decode_frame(ib, n, nullptr, cap, &ol, &sums);
+    out_len[m] = ol;
+    atomicAdd(&hdr[kFdEmpty], 1u);
+    if (sums) atomicAdd(&hdr[kFdSums], sums);
+    return;
+  }
+  if (force_serial) {
+    mc.route[m] = kRouteForced;
+    return;
+  }
+  if (!(h.flg & lz4f::kFlgIndep)) {
+    mc.route[m] = kRouteLinked;
+    return;
+  }
+  if (h.size == lz4f::kNoSize) {
+    mc.route[m] = kRouteNoSize;
+    return;
+  }
+  // fast route: every block but the last is full
+  mc.route[m] = kRouteRejected;
+  const u32 bs = h.block_max;
+  const u32 bsum = (h.flg & lz4f::kFlgBlockSum) ? 4 : 0;
+  const u32 nb = (u32)((h.size + bs - 1) / bs);
+  u64 ip = h.len, need = 0;
+  for (u32 k = 0; k < nb; ++k) {
+    if (n - ip < 4) return;
+    const u32 word = lz4f::rd32(ib + ip);
+    const u32 sz = word & ~lz4f::kRawBit;
+    ip += 4;
+    if (sz == 0 || sz > bs || n - ip < (u64)sz + bsum) return;
+    const u64 exp = h.size - (u64)k * bs < bs ? h.size - (u64)k * bs : bs;
+    if (word & lz4f::kRawBit) {
+      if (sz != exp) return;
+    } else {
+      need += dec_slot(sz);
+    }
+    ip += sz + bsum;
+  }
+  if (n - ip < 4 || lz4f::rd32(ib + ip) != 0) return;
+  ip += 4;
+  if (h.flg & lz4f::kFlgSum) {
+    if (n - ip < 4) return;
+    mc.xxh[m] = lz4f::rd32(ib + ip);
+    ip += 4;
+  }
+  if (ip != n) return;
+  const u32 base = atomicAdd(&hdr[kFdBlocks], nb);
+  u64 sb = atomicAdd(reinterpret_cast<unsigned long long*>(hdr + kFdStage), (unsigned long long)need);
+  if ((u64)base + nb > nb_cap || sb + need > stage_cap) return;
+  const u64 io = in_off[m], oo = out_off[m];
+  ip = h.len;
+  for (u32 k = 0; k < nb; ++k) {
+    const u32 e = base + k;
+    const u32 word = lz4f::rd32(ib + ip);
+    const u32 sz = word & ~lz4f::kRawBit;
+    const bool raw = word & lz4f::kRawBit;
+    ip += 4;
+    const u32 exp = (u32)(h.size - (u64)k * bs < bs ? h.size - (u64)k * bs : bs);
+    c.src_off[e] = io + ip;
+    c.src_len[e] = sz;
+    c.out_off[e] = oo + (u64)k * bs;
+    c.out_cap[e] = exp;
+    c.flags[e] = kBlkListed | (raw ? kBlkRaw : 0) | (bsum ? kBlkSum : 0);
+    if (!raw) {
+      c.in_off[e] = stage_off + sb;
+      c.in_len[e] = (u32)varint32_len(exp) + sz;
+      sb += dec_slot(sz);
+    }
+    ip += sz + bsum;
+  }
+  mc.first[m] = base;
+  mc.nb[m] = nb;
+  mc.route[m] = kRouteFast;
+}
+
+// One wave per listed block: a compressed block becomes a body of the block
+// decoder in the staging area, a raw block goes to its place in the slot.
+__global__ __launch_bounds__(256) void lz4f_stage_kernel(const u8* __restrict__ in, u8* out, u8* ws, BlockCols c,
+                                                       u32 nb_cap) {
+  const u32 lane = threadIdx.x & 63;
+  const u32 waves = gridDim.x * 4;
+  for (u32 e = blockIdx.x * 4 + (threadIdx.x >> 6); e < nb_cap; e += waves) {
+    const u32 f = c.flags[e];
+    if (!(f & kBlkListed)) continue;
+    const u8* src = in + c.src_off[e];
+    const u32 sz = c.src_len[e];
+    if (f & kBlkRaw) {
+      wave_copy(out + c.out_off[e], src, sz, lane);
+      continue;
+    }
+    u8* d = ws + c.in_off[e];
+    u32 v = c.out_cap[e];
+    const u32 hl = (u32)varint32_len(v);
+    if (lane == 0) {
+      u8* p = d;
+      while (v >= 0x80) {
+        *p++ = (u8)(v | 0x80);
+        v >>= 7;
+      }
+      *p = (u8)v;
+    }
+    wave_copy(d + hl, src, sz, lane);
+  }
+}
+
+// One lane per block entry: the block checksum over the stored bytes, and
+// what the block decoder said.
+__global__ __launch_bounds__(64) void lz4f_verdict_kernel(const u8* __restrict__ in, BlockCols c, u32 nb_cap,
+                                                        u32* hdr) {
+  const u32 e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= nb_cap) return;
+  const u32 f = c.flags[e];
+  const bool listed = f & kBlkListed;
+  bool fail = false;
+  if (listed && (f & kBlkSum)) {
+    const u8* src = in + c.src_off[e];
+    const u32 sz = c.src_len[e];
+    fail = lz4f::xxh32(src, sz) != lz4f::rd32(src + sz);
+  }
+  if (listed && !(f & kBlkRaw)) fail = fail || c.status[e] != kOk || c.out_len[e] != c.out_cap[e];
+  if (fail) c.flags[e] = f | kBlkFailed;
+  count_lanes(&hdr[kFdSums], listed && (f & kBlkSum));
+}
+
+// One lane per message: the fast route's answer (only ever FSG_OK), and the
+// serial decoder for everything else.
+__global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ in, const u64* __restrict__ in_off,
+                                                       const u32* __restrict__ in_len, u32 n_msgs, u8* out,
+                                                       const u64* __restrict__ out_off,
+                                                       const u32* __restrict__ out_cap, u32* __restrict__ out_len,
+                                                       i32* __restrict__ status, u32* hdr, MsgCols mc, BlockCols c,
+                                                       const u32* inner_fallback) {
+  const u32 m = blockIdx.x * 64 + threadIdx.x;
+  if (m == 0 && inner_fallback) hdr[kFdInner] = *inner_fallback;
+  if (m >= n_msgs) return;
+  u32 route = mc.route[m];
+  if (route == kRouteDone) return;
+  const u8* ib = in + in_off[m];
+  u8* ob = out + out_off[m];
+  u32 blocks = 0, sums = 0;
+  if (route == kRouteFast) {
+    const u32 first = mc.first[m], nb = mc.nb[m];
+    bool ok = true;
+    for (u32 k = 0; k < nb && ok; ++k) ok = !(c.flags[first + k] & kBlkFailed);
+    lz4f::Header h;
+    lz4f::parse_header(ib, in_len[m], &h);
+    if (ok && (h.flg & lz4f::kFlgSum)) {
+      ok = lz4f::xxh32(ob, h.size) == mc.xxh[m];
+      sums = 1;
+    }
+    if (ok) {
+      out_len[m] = (u32)h.size;
+      status[m] = kOk;
+      blocks = nb;
+    } else {
+      route = kRouteRejected;
+    }
+  }
+  if (route != kRouteFast) {
+    u32 ol, s = 0;
+    status[m] = lz4f::decode_frame(ib, in_len[m], ob, out_cap[m], &ol, &s);
+    out_len[m] = ol;
+    sums += s;
+  }
+  count_lanes(&hdr[kFdFastMsgs], route == kRouteFast);
+  count_lanes(&hdr[kFdLinked], route == kRouteLinked);
+  count_lanes(&hdr[kFdNoSize], route == kRouteNoSize);
+  count_lanes(&hdr[kFdRejected], route == kRouteRejected);
+  count_lanes(&hdr[kFdForced], route == kRouteForced);
+  if (blocks) atomicAdd(&hdr[kFdFastBlocks], blocks);
+  if (sums) atomicAdd(&hdr[kFdSums], sums);
+}
+
+// ---- workspace layouts
+u64 list_bytes(u64 n) { return round_up(n * 4, 256); }
+
+MsgCols msg_cols(u8* w, u32 n_msgs) {
+  MsgCols mc;
+  const u64 lb = list_bytes(n_msgs);
+  mc.route = reinterpret_cast<u32*>(w);
+  mc.first = reinterpret_cast<u32*>(w + lb);
+  mc.nb = reinterpret_cast<u32*>(w + 2 * lb);
+  mc.xxh = reinterpret_cast<u32*>(w + 3 * lb);
+  return mc;
+}
+u64 block_cols_bytes(u64 nb) { return round_up(nb * kBlockColBytes, 256); }
+BlockCols block_cols(u8* w, u64 nb) {
+  BlockCols c;
+  c.in_off = reinterpret_cast<u64*>(w);
+  c.out_off = c.in_off + nb;
+  c.src_off = c.out_off + nb;
+  c.in_len = reinterpret_cast<u32*>(c.src_off + nb);
+  c.out_cap = c.in_len + nb;
+  c.out_len = c.out_cap + nb;
+  c.status = reinterpret_cast<i32*>(c.out_len + nb);
+  c.src_len = reinterpret_cast<u32*>(c.status + nb);
+  c.flags = c.src_len + nb;
+  return c;
+}
+
+// A workspace for `total` input bytes: header | message columns | block
+// columns | [compress: a 64-byte slot per entry] | the block codec's workspace
+// | staging.
+struct Plan {
+  u32 nb_cap;
+  u64 stage_cap;
+  u64 off_msg, off_blk, off_dummy, off_inner, inner_bytes, off_stage, total;
+};
+constexpr u64 kMaxBlocks = 1ull << 30;
+
+bool enc_plan(u32 n_msgs, u64 total, u32 id, Plan* p) {
+  const u64 bs = lz4f::block_bytes(id);
+  const u64 nb = (u64)n_msgs + total / bs;
+  if (nb > kMaxBlocks) return false;
+  p->nb_cap = (u32)nb;
+  p->stage_cap = total + total / 255 + nb * (enc_slot(0) + 16);
+  p->off_msg = kHead;
+  p->off_blk = p->off_msg + 4 * list_bytes(n_msgs);
+  p->off_dummy = p->off_blk + block_cols_bytes(nb);
+  p->off_inner = p->off_dummy + round_up(64 * nb, 256);
+  p->inner_bytes = lz4_compress_workspace_bytes((u32)nb);
+  p->off_stage = round_up(p->off_inner + p->inner_bytes, 256);
+  p->total = p->off_stage + round_up(p->stage_cap, 256);
+  return true;
+}
+
+// a full compressed block of the smallest size, 64 KiB, has at least 257
+// bytes (a length byte adds at most 255), so a frame the fast route takes has
+// at most one block per 256 input bytes and one more
+bool dec_plan(u32 n_msgs, u64 total, Plan* p) {
+  const u64 nb = (u64)n_msgs + total / 256;
+  if (nb > kMaxBlocks) return false;
+  p->nb_cap = (u32)nb;
+  p->stage_cap = total + 32 * nb;
+  p->off_msg = kHead;
+  p->off_blk = p->off_msg + 4 * list_bytes(n_msgs);
+  p->off_dummy = p->off_blk + block_cols_bytes(nb);
+  p->off_inner = p->off_dummy;
+  // the block decoder's workspace: its columns for every entry, and a bitmap
+  // for `total` block bytes with 16 bytes of rounding for a block per message
+  // and per 4 KiB (64 KiB blocks that shrank 16 times).  Blocks past that go
+  // to the block decoder's one-pass kernel: slower, the same bytes.
+  p->inner_bytes = lz4_decode_workspace_bytes((u32)nb, 0) - 16 * nb + 16 * ((u64)n_msgs + total / 4096) +
+                   4 * (total / 32);
+  p->off_stage = round_up(p->off_inner + p->inner_bytes, 256);
+  p->total = p->off_stage + round_up(p->stage_cap, 256);
+  return true;
+}
+
+// the largest `total` whose workspace fits ws_bytes (the calls get no input
+// size: the workspace says what it was sized for); false below total = 0
+template <typename F>
+bool plan_for(size_t ws_bytes, Plan* p, F make) {
+  if (!make(0, p) || p->total > ws_bytes) return false;
+  u64 lo = 0, hi = 1ull << 46;  // make(lo) fits
+  while (lo + 1 < hi) {
+    const u64 mid = lo + (hi - lo) / 2;
+    Plan q;
+    if (make(mid, &q) && q.total <= ws_bytes) lo = mid;
+    else hi = mid;
+  }
+  return make(lo, p);
+}
+
+}  // namespace
+
+size_t lz4f_compress_workspace_bytes(u32 n_msgs, u64 total_in_bytes, u32 id) {
+  Plan p;
+  return enc_plan(n_msgs, total_in_bytes, id, &p) ? (size_t)p.total : 0;
+}
+size_t lz4f_decompress_workspace_bytes(u32 n_msgs, u64 total_in_bytes) {
+  Plan p;
+  return dec_plan(n_msgs, total_in_bytes, &p) ? (size_t)p.total : 0;
+}
+u32 lz4f_compress_block_capacity(u32 n_msgs, size_t ws_bytes, u32 id) {
+  Plan p;
+  return plan_for(ws_bytes, &p, [&](u64 t, Plan* q) { return enc_plan(n_msgs, t, id, q); }) ? p.nb_cap : 0;
+}
+u32 lz4f_decompress_block_capacity(u32 n_msgs, size_t ws_bytes) {
+  Plan p;
+  return plan_for(ws_bytes, &p, [&](u64 t, Plan* q) { return dec_plan(n_msgs, t, q); }) ? p.nb_cap : 0;
+}
+
+void lz4f_encode_header_counts(const void* header, Lz4fEncodeHeaderCounts* c) {
+  u32 ctr[8];
+  __builtin_memcpy(ctr, header, sizeof(ctr));
+  c->blocks = ctr[kFcListed];
+  c->raw_blocks = ctr[kFcRaw];
+  c->overflow_messages = ctr[kFcOverflow];
+}
+void lz4f_decode_header_counts(const void* header, Lz4fDecodeHeaderCounts* c) {
+  u32 ctr[12];
+  __builtin_memcpy(ctr, header, sizeof(ctr));
+  c->fast_messages = ctr[kFdFastMsgs];
+  c->fast_blocks = ctr[kFdFastBlocks];
+  c->empty_messages = ctr[kFdEmpty];
+  c->serial_linked = ctr[kFdLinked];
+  c->serial_no_size = ctr[kFdNoSize];
+  c->serial_rejected = ctr[kFdRejected];
+  c->serial_forced = ctr[kFdForced];
+  c->checksummed_units = ctr[kFdSums];
+  c->inner_fallback = ctr[kFdInner];
+}
+
+hipError_t launch_lz4f_encode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
+                              const u64* out_off, u32* out_len, i32* status, u32 id, u32 flags, void* ws,
+                              size_t ws_bytes, u64 wave_min, hipStream_t stream) {
+  if (n_msgs == 0) return hipSuccess;
+  Plan p;
+  if (id < lz4f::kMinBlockId || id > lz4f::kMaxBlockId ||
+      !plan_for(ws_bytes, &p, [&](u64 t, Plan* q) { return enc_plan(n_msgs, t, id, q); }))
+    return hipErrorInvalidValue;
+  u8* const w = static_cast<u8*>(ws);
+  u32* const hdr = reinterpret_cast<u32*>(w);
+  const MsgCols mc = msg_cols(w + p.off_msg, n_msgs);
+  const BlockCols c = block_cols(w + p.off_blk, p.nb_cap);
+  const u32 bs = lz4f::block_bytes(id);
+  hipError_t e = hipMemsetAsync(w, 0, kHead, stream);
+  if (e != hipSuccess) return e;
+  lz4f_prefill_kernel<<<(p.nb_cap + 255) / 256, 256, 0, stream>>>(c, p.nb_cap, p.off_dummy);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  lz4f_plan_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in_off, in_len, n_msgs, bs, hdr, mc, c, p.nb_cap,
+                                                         p.off_stage, p.stage_cap);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  // the block encoders on the block columns, with their own routing
+  e = launch_lz4_encode(in, c.in_off, c.in_len, p.nb_cap, w, c.out_off, c.out_len, c.status, w + p.off_inner,
+                        p.inner_bytes, wave_min, stream);
+  if (e != hipSuccess) return e;
+  if (flags & 1) {
+    lz4f_xxh_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, mc.xxh);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  lz4f_assemble_kernel<<<n_msgs, 64, 0, stream>>>(in, in_len, out, out_off, out_len, status, id, flags & 1, hdr, mc, c,
+                                                  w);
+  return hipGetLastError();
+}
+
+hipError_t launch_lz4f_content_sizes(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* sizes,
+                                     i32* status, hipStream_t stream) {
+  if (n_msgs == 0) return hipSuccess;
+  lz4f_sizes_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, sizes, status);
+  return hipGetLastError();
+}
+
+hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
+                              const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
+                              size_t ws_bytes, bool force_serial, hipStream_t stream) {
+  if (n_msgs == 0) return hipSuccess;
+  Plan p;
+  if (!plan_for(ws_bytes, &p, [&](u64 t, Plan* q) { return dec_plan(n_msgs, t, q); })) return hipErrorInvalidValue;
+  u8* const w = static_cast<u8*>(ws);
+  u32* const hdr = reinterpret_cast<u32*>(w);
+  const MsgCols mc = msg_cols(w + p.off_msg, n_msgs);
+  const BlockCols c = block_cols(w + p.off_blk, p.nb_cap);
+  // header, message and block columns: an entry nobody lists stays an empty
+  // body, which the block decoder answers without touching the output
+  hipError_t e = hipMemsetAsync(w, 0, p.off_dummy, stream);
+  if (e != hipSuccess) return e;
+  lz4f_index_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out_off, out_cap, out_len,
+                                                          status, hdr, mc, c, p.nb_cap, p.off_stage, p.stage_cap,
+                                                          force_serial ? 1u : 0u);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const u32* inner_fallback = nullptr;
+  if (!force_serial) {
+    const u32 grid = (p.nb_cap + 3) / 4 < 8192 ? (p.nb_cap + 3) / 4 : 8192;
+    lz4f_stage_kernel<<<grid, 256, 0, stream>>>(in, out, w, c, p.nb_cap);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    e = launch_lz4_decode2(w, c.in_off, c.in_len, p.nb_cap, out, c.out_off, c.out_cap, c.out_len, c.status,
+                           w + p.off_inner, p.inner_bytes, stream, nullptr);
+    if (e != hipSuccess) return e;
+    lz4f_verdict_kernel<<<(p.nb_cap + 63) / 64, 64, 0, stream>>>(in, c, p.nb_cap, hdr);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    inner_fallback = reinterpret_cast<const u32*>(w + p.off_inner) + 3;  // lz4_decode2.hip: its fallback counter
+  }
+  lz4f_finish_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_cap, out_len,
+                                                           status, hdr, mc, c, inner_fallback);
+  return hipGetLastError();
+}
+
+}  // namespace fsg

@@ -1,0 +1,280 @@
+// lz4_frame_format.h -- the LZ4 frame format (1.6.x) in plain C++: XXH32, the
+// descriptor, and the serial frame decoder.  One text for three users: the
+// device code (lz4_frame.hip, where LZ4F_HD is __host__ __device__), the host
+// codec (host/lz4_cpu.cc, compiled by g++) and tests/cpp/lz4f_host_check.hip,
+// which runs the decoder on the CPU under AddressSanitizer.
+// include/flare_lz4_gpu.h states the rules ("LZ4 frames").
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define LZ4F_HD __host__ __device__ inline
+#else
+#define LZ4F_HD inline
+#endif
+
+namespace lz4f {
+
+constexpr uint32_t kMagic = 0x184D2204u;
+constexpr uint32_t kRawBit = 0x80000000u;   // block size word: the block is stored raw
+constexpr uint32_t kMinBlockId = 4, kMaxBlockId = 7;
+constexpr uint64_t kNoSize = ~0ull;         // content size: the frame states none
+// status words (include/flare_snappy_gpu.h)
+constexpr int32_t kStOk = 0, kStCorrupt = 1, kStBadHeader = 2, kStSlotTooSmall = 3;
+// FLG bits
+constexpr uint32_t kFlgIndep = 0x20, kFlgBlockSum = 0x10, kFlgSize = 0x08, kFlgSum = 0x04, kFlgReserved = 0x02,
+                   kFlgDict = 0x01;
+
+LZ4F_HD uint32_t block_bytes(uint32_t id) { return 1u << (8 + 2 * id); }  // 4..7: 64 KiB, 256 KiB, 1 MiB, 4 MiB
+
+LZ4F_HD uint32_t rd32(const uint8_t* p) {
+  return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
+LZ4F_HD void wr32(uint8_t* p, uint32_t v) {
+  p[0] = (uint8_t)v;
+  p[1] = (uint8_t)(v >> 8);
+  p[2] = (uint8_t)(v >> 16);
+  p[3] = (uint8_t)(v >> 24);
+}
+
+// ---- XXH32
+constexpr uint32_t kP1 = 2654435761u, kP2 = 2246822519u, kP3 = 3266489917u, kP4 = 668265263u, kP5 = 374761393u;
+LZ4F_HD uint32_t rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
+LZ4F_HD uint32_t xxh_round(uint32_t acc, uint32_t in) { return rotl(acc + in * kP2, 13) * kP1; }
+
+LZ4F_HD uint32_t xxh32(const uint8_t* p, uint64_t n, uint32_t seed = 0) {
+  uint64_t i = 0;
+  uint32_t h;
+  if (n >= 16) {
+    uint32_t v1 = seed + kP1 + kP2, v2 = seed + kP2, v3 = seed, v4 = seed - kP1;
+    for (; i + 16 <= n; i += 16) {
+      v1 = xxh_round(v1, rd32(p + i));
+      v2 = xxh_round(v2, rd32(p + i + 4));
+      v3 = xxh_round(v3, rd32(p + i + 8));
+      v4 = xxh_round(v4, rd32(p + i + 12));
+    }
+    h = rotl(v1, 1) + rotl(v2, 7) + rotl(v3, 12) + rotl(v4, 18);
+  } else {
+    h = seed + kP5;
+  }
+  h += (uint32_t)n;
+  for (; i + 4 <= n; i += 4) h = rotl(h + rd32(p + i) * kP3, 17) * kP4;
+  for (; i < n; ++i) h = rotl(h + p[i] * kP5, 11) * kP1;
+  h ^= h >> 15;
+  h *= kP2;
+  h ^= h >> 13;
+  h *= kP3;
+  h ^= h >> 16;
+  return h;
+}
+
+// ---- descriptor
+struct Header {
+  uint32_t len;         // bytes up to and including HC
+  uint32_t block_max;   // block_bytes(id)
+  uint32_t flg;
+  uint64_t size;        // content size, kNoSize when the frame states none
+};
+
+// kStOk or kStBadHeader: a bad magic number (skippable and legacy ones too),
+// version, reserved bit, block size id or HC, a descriptor cut short, DictID.
+LZ4F_HD int32_t parse_header(const uint8_t* p, uint64_t n, Header* h) {
+  h->size = kNoSize;
+  if (n < 7 || rd32(p) != kMagic) return kStBadHeader;
+  const uint32_t flg = p[4], bd = p[5];
+  if ((flg >> 6) != 1 || (flg & (kFlgReserved | kFlgDict))) return kStBadHeader;
+  const uint32_t id = (bd >> 4) & 7;
+  if ((bd & 0x8F) || id < kMinBlockId) return kStBadHeader;
+  const uint32_t len = 7 + ((flg & kFlgSize) ? 8 : 0);
+  if (n < len) return kStBadHeader;
+  if (((xxh32(p + 4, len - 5) >> 8) & 0xFF) != p[len - 1]) return kStBadHeader;
+  h->len = len;
+  h->block_max = block_bytes(id);
+  h->flg = flg;
+  if (flg & kFlgSize) h->size = (uint64_t)rd32(p + 6) | (uint64_t)rd32(p + 10) << 32;
+  return kStOk;
+}
+
+// The block size id LZ4F_compressFrame puts in BD: the smallest one, up to
+// the id asked for, whose block holds all n bytes (LZ4F_optimalBSID).  The
+// blocks are the same either way: such a message is one block.
+LZ4F_HD uint32_t frame_block_id(uint64_t n, uint32_t id) {
+  uint32_t p = kMinBlockId;
+  while (p < id && n > block_bytes(p)) ++p;
+  return p;
+}
+
+// The descriptor the compressor writes (independent blocks, no block
+// checksums; the content size unless n is 0, which LZ4F_compressFrame reads as
+// "unknown"); returns its length, 7 or 15.
+LZ4F_HD uint32_t write_header(uint8_t* p, uint64_t n, uint32_t id, bool checksum) {
+  wr32(p, kMagic);
+  p[4] = (uint8_t)(0x40 | kFlgIndep | (n ? kFlgSize : 0) | (checksum ? kFlgSum : 0));
+  p[5] = (uint8_t)(frame_block_id(n, id) << 4);
+  uint32_t len = 6;
+  if (n) {
+    wr32(p + 6, (uint32_t)n);
+    wr32(p + 10, (uint32_t)(n >> 32));
+    len = 14;
+  }
+  p[len] = (uint8_t)(xxh32(p + 4, len - 4) >> 8);
+  return len + 1;
+}
+
+// Frame bound for the compressor's settings: descriptor 15, a size word per
+// block, the bytes themselves (a block that does not shrink is stored raw),
+// the end mark and a content checksum.  LZ4F_compressFrameBound gives 19 (its
+// largest descriptor, with DictID) in place of 15.
+LZ4F_HD uint64_t max_frame_length(uint64_t n, uint32_t id) {
+  const uint64_t bs = block_bytes(id);
+  return 15 + 4 * ((n + bs - 1) / bs) + n + 4 + 4;
+}
+
+// ---- blocks
+// n bytes forward, 16 at a time then singly; source and destination apart
+// (raw blocks, literals)
+LZ4F_HD void copy_bytes(uint8_t* d, const uint8_t* s, uint64_t n) {
+  uint64_t k = 0;
+  for (; k + 16 <= n; k += 16) __builtin_memcpy(d + k, s + k, 16);
+  for (; k < n; ++k) d[k] = s[k];
+}
+
+// Decoded length of a block from its sequences' lengths alone: the sequence
+// whose literals end at the block's last byte is the last one.  false: no such
+// sequence, or more than `limit` bytes.
+LZ4F_HD bool block_length(const uint8_t* src, uint32_t n, uint64_t limit, uint64_t* len) {
+  uint64_t ip = 0, op = 0;
+  for (;;) {
+    if (ip >= n) return false;
+    const uint32_t token = src[ip++];
+    uint64_t lit = token >> 4;
+    if (lit == 15) {
+      uint32_t b;
+      do {
+        if (ip >= n) return false;
+        b = src[ip++];
+        lit += b;
+      } while (b == 255);
+    }
+    if (lit > n - ip || op + lit > limit) return false;
+    if (ip + lit == n) {
+      *len = op + lit;
+      return true;
+    }
+    ip += lit + 2;
+    if (ip > n) return false;
+    uint64_t ml = (token & 15) + 4;
+    if ((token & 15) == 15) {
+      uint32_t b;
+      do {
+        if (ip >= n) return false;
+        b = src[ip++];
+        ml += b;
+      } while (b == 255);
+    }
+    op += lit + ml;
+    if (op > limit) return false;
+  }
+}
+
+// One block to exactly ulen bytes at dst, by the rules of lz4.hip's
+// lz4_decompress_block (the end rules against ulen, offset 0 rejected); a
+// match may reach `hist` bytes back before dst (linked blocks: the bytes the
+// frame has produced so far; an offset is at most 65,535).
+LZ4F_HD bool block_decode(const uint8_t* src, uint32_t n, uint8_t* dst, uint32_t ulen, uint64_t hist) {
+  uint32_t ip = 0, op = 0;
+  for (;;) {
+    if (ip >= n) return false;
+    const uint32_t token = src[ip++];
+    uint32_t lit = token >> 4;
+    if (lit == 15) {
+      uint32_t b;
+      do {
+        if (ip >= n) return false;
+        b = src[ip++];
+        lit += b;
+      } while (b == 255 && lit <= n);
+    }
+    if (lit > n - ip || lit > ulen - op) return false;
+    const bool last = (uint64_t)op + lit + 12 > ulen || (uint64_t)ip + lit + 8 > n;
+    if (last && ip + lit != n) return false;
+    copy_bytes(dst + op, src + ip, lit);
+    if (last) return op + lit == ulen;
+    ip += lit;
+    op += lit;
+    const uint32_t off = (uint32_t)src[ip] | ((uint32_t)src[ip + 1] << 8);
+    ip += 2;
+    if (off == 0 || off > op + hist) return false;
+    uint32_t ml = (token & 15) + 4;
+    if ((token & 15) == 15) {
+      uint32_t b;
+      do {
+        if (ip >= n) return false;
+        b = src[ip++];
+        ml += b;
+      } while (b == 255 && ml <= ulen);
+    }
+    if ((uint64_t)ml + 5 > ulen - op) return false;
+    uint8_t* d = dst + op;
+    const uint8_t* from = d - off;
+    for (uint32_t k = 0; k < ml; ++k) d[k] = from[k];
+    op += ml;
+  }
+}
+
+// ---- the serial frame decoder: one frame per body, every write below
+// out + cap.  *out_len: the decoded length on kStOk, min(content size, 2^32-1)
+// on kStSlotTooSmall, else 0.  *checksums (may be null): block and content
+// checksums verified.
+LZ4F_HD int32_t decode_frame(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint32_t* out_len,
+                             uint32_t* checksums = nullptr) {
+  *out_len = 0;
+  Header h;
+  if (parse_header(in, n, &h) != kStOk) return kStBadHeader;
+  if (h.size != kNoSize && h.size > cap) {
+    *out_len = h.size > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)h.size;
+    return kStSlotTooSmall;
+  }
+  const uint64_t limit = h.size != kNoSize ? h.size : cap;
+  const uint32_t bsum = (h.flg & kFlgBlockSum) ? 4 : 0;
+  uint64_t ip = h.len, op = 0;
+  uint32_t sums = 0;
+  for (;;) {
+    if (n - ip < 4) return kStCorrupt;
+    const uint32_t word = rd32(in + ip);
+    ip += 4;
+    if (word == 0) break;
+    const uint32_t size = word & ~kRawBit;
+    if (size > h.block_max || n - ip < (uint64_t)size + bsum) return kStCorrupt;
+    const uint8_t* blk = in + ip;
+    ip += size + bsum;
+    if (bsum) {
+      if (xxh32(blk, size) != rd32(blk + size)) return kStCorrupt;
+      ++sums;
+    }
+    if (word & kRawBit) {
+      if (size > limit - op) return kStCorrupt;
+      copy_bytes(out + op, blk, size);
+      op += size;
+      continue;
+    }
+    const uint64_t room = limit - op < h.block_max ? limit - op : h.block_max;
+    uint64_t len;
+    if (!block_length(blk, size, room, &len)) return kStCorrupt;
+    if (!block_decode(blk, size, out + op, (uint32_t)len, (h.flg & kFlgIndep) ? 0 : op)) return kStCorrupt;
+    op += len;
+  }
+  if (h.flg & kFlgSum) {
+    if (n - ip < 4 || xxh32(out, op) != rd32(in + ip)) return kStCorrupt;
+    ip += 4;
+    ++sums;
+  }
+  if (ip != n || (h.size != kNoSize && op != h.size)) return kStCorrupt;
+  *out_len = (uint32_t)op;
+  if (checksums) *checksums = sums;
+  return kStOk;
+}
+
+}  // namespace lz4f

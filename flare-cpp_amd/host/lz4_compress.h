@@ -20,10 +20,24 @@ bool Lz4Decompress(const cord_buf& data, Message* msg);
 bool Lz4Compress(const cord_buf& in, cord_buf* out);
 bool Lz4Decompress(const cord_buf& in, cord_buf* out);
 
+// The same four functions on standard LZ4 frames (LZ4 Frame Format 1.6.x,
+// include/flare_lz4_gpu.h "LZ4 frames"): what LZ4F_compressFrame writes with
+// independent 64 KiB blocks and a content size, and one frame per body back
+// (any block size, linked blocks and checksums included), so a peer that
+// fills COMPRESS_TYPE_LZ4 with liblz4 interoperates.
+bool Lz4FrameCompress(const Message& msg, cord_buf* buf);
+bool Lz4FrameDecompress(const cord_buf& data, Message* msg);
+bool Lz4FrameCompress(const cord_buf& in, cord_buf* out);
+bool Lz4FrameDecompress(const cord_buf& in, cord_buf* out);
+
 }  // namespace flare::rpc::policy
 
 namespace flare::rpc {
 // Registers the LZ4 handler at COMPRESS_TYPE_LZ4 once per process; 0 on
 // success.
 int GlobalInitializeLz4();
+// Registers the frame handler at COMPRESS_TYPE_LZ4 instead: an integrator
+// calls this or GlobalInitializeLz4(), not both (the second registration of a
+// type fails).
+int GlobalInitializeLz4Frame();
 }  // namespace flare::rpc

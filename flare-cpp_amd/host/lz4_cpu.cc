@@ -4,6 +4,8 @@
 #include <cstring>
 #include <vector>
 
+#include "../csrc/lz4_frame_format.h"
+
 namespace flare::lz4::cpu {
 
 namespace {
@@ -218,6 +220,47 @@ size_t Compress(const uint8_t* in, size_t n, uint8_t* out) {
     if (v < 128) break;
   }
   return h + CompressBlock(in, n, out + h);
+}
+
+// ---- frames (csrc/lz4_frame_format.h: the format text the device code uses)
+uint32_t Xxh32(const uint8_t* in, size_t n, uint32_t seed) { return lz4f::xxh32(in, n, seed); }
+
+size_t MaxFrameLength(size_t n, int block_size_id) {
+  if (block_size_id < 4 || block_size_id > 7) return 0;
+  return lz4f::max_frame_length(n, static_cast<uint32_t>(block_size_id));
+}
+
+size_t CompressFrame(const uint8_t* in, size_t n, uint8_t* out, int block_size_id, bool content_checksum) {
+  if (block_size_id < 4 || block_size_id > 7) return 0;
+  const uint32_t id = static_cast<uint32_t>(block_size_id);
+  const size_t bs = lz4f::block_bytes(id);
+  size_t op = lz4f::write_header(out, n, id, content_checksum);
+  std::vector<uint8_t> blk(BlockBound(bs));
+  for (size_t ip = 0; ip < n; ip += bs) {
+    const size_t len = n - ip < bs ? n - ip : bs;
+    const size_t c = CompressBlock(in + ip, len, blk.data());
+    const bool raw = c >= len;  // a block that does not shrink is stored as it is
+    lz4f::wr32(out + op, raw ? static_cast<uint32_t>(len) | lz4f::kRawBit : static_cast<uint32_t>(c));
+    std::memcpy(out + op + 4, raw ? in + ip : blk.data(), raw ? len : c);
+    op += 4 + (raw ? len : c);
+  }
+  lz4f::wr32(out + op, 0);
+  op += 4;
+  if (content_checksum) {
+    lz4f::wr32(out + op, lz4f::xxh32(in, n));
+    op += 4;
+  }
+  return op;
+}
+
+int DecompressFrame(const uint8_t* in, size_t n, uint8_t* out, size_t cap, uint32_t* out_len) {
+  return lz4f::decode_frame(in, n, out, cap, out_len);
+}
+
+uint64_t FrameContentSize(const uint8_t* in, size_t n, int* status) {
+  lz4f::Header h;
+  *status = lz4f::parse_header(in, n, &h);
+  return h.size;
 }
 
 }  // namespace flare::lz4::cpu

@@ -40,4 +40,18 @@ bool DecompressBlock(const uint8_t* in, size_t n, uint8_t* out, size_t ulen);
 size_t Compress(const uint8_t* in, size_t n, uint8_t* out);
 size_t ReadHeader(const uint8_t* in, size_t n, uint32_t* ulen);
 
+// ---- LZ4 frames (LZ4 Frame Format 1.6.x; include/flare_lz4_gpu.h, "LZ4
+// frames", states the rules).  Same bytes and verdicts as the GPU calls.
+uint32_t Xxh32(const uint8_t* in, size_t n, uint32_t seed = 0);
+// n + 4 * ceil(n / block size) + 23; 0 for an id outside 4..7
+size_t MaxFrameLength(size_t n, int block_size_id);
+// The bytes of LZ4F_compressFrame (independent blocks, content size, level 0,
+// no block checksums) into out (MaxFrameLength bytes); returns the length.
+size_t CompressFrame(const uint8_t* in, size_t n, uint8_t* out, int block_size_id, bool content_checksum);
+// One frame to out (cap bytes): 0 ok, 1 corrupt, 2 bad header, 3 content size
+// above cap (the FSG_* status words); *out_len as d_out_len of the GPU call.
+int DecompressFrame(const uint8_t* in, size_t n, uint8_t* out, size_t cap, uint32_t* out_len);
+// The descriptor's content size (~0 when it states none); *status 0 or 2.
+uint64_t FrameContentSize(const uint8_t* in, size_t n, int* status);
+
 }  // namespace flare::lz4::cpu

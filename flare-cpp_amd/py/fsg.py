@@ -41,6 +41,13 @@ EncodeReport = _report_struct("EncodeReport", (
 # struct fsg_lz4_encode_report (include/flare_lz4_gpu.h)
 Lz4EncodeReport = _report_struct("Lz4EncodeReport", (
     "path", "lane_messages", "wave_messages", "wave_bytes", "wave_min"))
+# struct fsg_lz4f_encode_report / fsg_lz4f_decode_report (include/flare_lz4_gpu.h, "LZ4 frames")
+Lz4fEncodeReport = _report_struct("Lz4fEncodeReport", (
+    "blocks", "raw_blocks", "overflow_messages", "block_entries", "block_wave_min"))
+Lz4fDecodeReport = _report_struct("Lz4fDecodeReport", (
+    "fast_messages", "fast_blocks", "empty_messages", "serial_linked", "serial_no_size", "serial_rejected",
+    "serial_forced", "checksummed_units", "inner_fallback_blocks", "block_entries"))
+LZ4F_NO_CONTENT_SIZE = 0xFFFFFFFFFFFFFFFF
 PATH_MAIN, PATH_SINGLE_DESIGN, PATH_NO_WORKSPACE, PATH_FORCED = 0, 1, 2, 3
 
 _SIGS = {
@@ -81,6 +88,14 @@ _SIGS = {
     "fsg_lz4_decompress_batch_ws": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "fsg_lz4_decompress_batch_2s": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
                                                _vp]),
+    "fsg_lz4f_max_frame_length": (_sz, [_sz, _u32]),
+    "fsg_lz4f_compress_workspace_bytes": (_sz, [_u32, _u64, _u32]),
+    "fsg_lz4f_compress_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _sz, _vp]),
+    "fsg_lz4f_decompress_workspace_bytes": (_sz, [_u32, _u64]),
+    "fsg_lz4f_decompress_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "fsg_lz4f_content_sizes_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "fsg_lz4f_compress_report": (_c.c_int, [_vp, _u32, _sz, _u32, _c.POINTER(Lz4fEncodeReport)]),
+    "fsg_lz4f_decompress_report": (_c.c_int, [_vp, _u32, _sz, _c.POINTER(Lz4fDecodeReport)]),
 }
 
 
@@ -96,7 +111,10 @@ def header_symbols(header: Path | None = None) -> list[str]:
 _OPTIONAL = {"fsg_decompress_batch_2s", "fsg_decompress_batch_partial", "fsg_decompress_batch_iovec", "fsg_lz4_decompress_batch_2s", "fsg_lz4_decompress_batch_ws",
              "fsg_lz4_decompress_workspace_bytes", "fsg_set_option", "fsg_get_option", "fsg_default_option",
              "fsg_pack_workspace_bytes", "fsg_pack_batch", "fsg_report_header_bytes", "fsg_decompress_report",
-             "fsg_compress_report", "fsg_lz4_decompress_report", "fsg_lz4_compress_report"}
+             "fsg_compress_report", "fsg_lz4_decompress_report", "fsg_lz4_compress_report",
+             "fsg_lz4f_max_frame_length", "fsg_lz4f_compress_workspace_bytes", "fsg_lz4f_compress_batch",
+             "fsg_lz4f_decompress_workspace_bytes", "fsg_lz4f_decompress_batch", "fsg_lz4f_content_sizes_batch",
+             "fsg_lz4f_compress_report", "fsg_lz4f_decompress_report"}
 
 
 def load_gpu_lib(path: Path | None = None) -> ctypes.CDLL:
@@ -274,6 +292,55 @@ class SnappyGPU:
         else:
             self._check(self.lib.fsg_lz4_decompress_batch_2s(*args, self._stream(pass1_stream)),
                         "fsg_lz4_decompress_batch_2s")
+
+    # ---- LZ4 frames (include/flare_lz4_gpu.h, "LZ4 frames")
+    def lz4f_compress_workspace(self, n, total_in_bytes, block_size_id=4, device=None):
+        import torch
+        nbytes = self.lib.fsg_lz4f_compress_workspace_bytes(n, total_in_bytes, block_size_id)
+        return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device or f"cuda:{self.device}")
+
+    def lz4f_compress(self, d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_len, d_status, workspace,
+                      block_size_id=4, checksum=False, stream=None):
+        """fsg_lz4f_compress_batch: standard LZ4 frames, slots of
+        fsg_lz4f_max_frame_length(len, block_size_id) bytes."""
+        ws = 0 if workspace is None else workspace.numel() * workspace.element_size()
+        self._check(self.lib.fsg_lz4f_compress_batch(
+            _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len),
+            _ptr(d_status), block_size_id, 1 if checksum else 0, _ptr(workspace), ws, self._stream(stream)),
+            "fsg_lz4f_compress_batch")
+
+    def lz4f_decompress_workspace(self, n, total_in_bytes, device=None):
+        import torch
+        nbytes = self.lib.fsg_lz4f_decompress_workspace_bytes(n, total_in_bytes)
+        return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device or f"cuda:{self.device}")
+
+    def lz4f_decompress(self, d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len, d_status,
+                        workspace, stream=None):
+        ws = 0 if workspace is None else workspace.numel() * workspace.element_size()
+        self._check(self.lib.fsg_lz4f_decompress_batch(
+            _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_out), _ptr(d_out_off), _ptr(d_out_cap),
+            _ptr(d_out_len), _ptr(d_status), _ptr(workspace), ws, self._stream(stream)),
+            "fsg_lz4f_decompress_batch")
+
+    def lz4f_content_sizes(self, d_in, d_in_off, d_in_len, n, d_content_size, d_status, stream=None):
+        """fsg_lz4f_content_sizes_batch (d_content_size int64 / uint64:
+        LZ4F_NO_CONTENT_SIZE where the frame states none)."""
+        self._check(self.lib.fsg_lz4f_content_sizes_batch(
+            _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_content_size), _ptr(d_status),
+            self._stream(stream)), "fsg_lz4f_content_sizes_batch")
+
+    def lz4f_compress_report(self, workspace, n, block_size_id=4) -> dict:
+        head, nbytes = self._report_header(workspace)
+        r = Lz4fEncodeReport()
+        self._check(self.lib.fsg_lz4f_compress_report(head, n, nbytes, block_size_id, _c.byref(r)),
+                    "fsg_lz4f_compress_report")
+        return self._report_dict(r)
+
+    def lz4f_decompress_report(self, workspace, n) -> dict:
+        head, nbytes = self._report_header(workspace)
+        r = Lz4fDecodeReport()
+        self._check(self.lib.fsg_lz4f_decompress_report(head, n, nbytes, _c.byref(r)), "fsg_lz4f_decompress_report")
+        return self._report_dict(r)
 
     # ---- path reports (fsg_decompress_report and its kin)
     def _report_header(self, workspace):

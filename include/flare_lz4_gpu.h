@@ -147,6 +147,148 @@ int fsg_lz4_compress_report(const void *header_host_copy, uint32_t n_msgs,
                             size_t workspace_bytes,
                             struct fsg_lz4_encode_report *out);
 
+/* ------------------------------------------------------------------------
+ * LZ4 frames: bodies in the LZ4 Frame Format 1.6.x, which LZ4F_compressFrame
+ * and the lz4 command write and read.  The body format above is untouched.
+ *
+ * Descriptor.  Magic 0x184D2204 (little endian); FLG = version 01 (bits 7-6),
+ * B.Indep (5), B.Checksum (4), C.Size (3), C.Checksum (2), reserved 0 (1),
+ * DictID (0); BD = block size id 4..7 in bits 6-4 (64 KiB, 256 KiB, 1 MiB,
+ * 4 MiB), every other bit 0; the 8-byte content size when C.Size is set;
+ * HC = (XXH32(descriptor bytes from FLG through the last optional field,
+ * seed 0) >> 8) & 0xFF.  Then blocks: a 4-byte size word (bit 31: stored raw),
+ * the bytes, a 4-byte XXH32 of the bytes as stored when B.Checksum is set;
+ * a zero size word ends them; then the XXH32 of the content when C.Checksum
+ * is set.
+ *
+ * The compressor writes exactly the bytes of LZ4F_compressFrame (liblz4
+ * 1.9.x) with blockMode = independent, blockSizeID as asked for, contentSize =
+ * n, compression level 0, no block checksums, a content checksum when flag
+ * bit 0 asks for it: every block is LZ4_compress_default of its bytes, stored
+ * raw when that is not shorter than they are.  As there, BD holds the smallest
+ * id, up to the one asked for, whose block holds the whole message (a message
+ * of at most 64 KiB says id 4 whatever was asked).  An empty message has no C.Size
+ * field and no blocks (liblz4 reads contentSize 0 as "unknown"): 11 bytes.
+ *
+ * The decompressor accepts one frame per body; bytes after it are
+ * FSG_CORRUPT.  FSG_BAD_HEADER: a bad magic number (the skippable and legacy
+ * ones included), version, reserved bit, block size id below 4 or HC, a
+ * descriptor cut short, DictID set (no dictionaries here).  A content size
+ * above d_out_cap[i] is FSG_SLOT_TOO_SMALL with d_out_len[i] = min(content
+ * size, 2^32 - 1).  Everything else wrong is FSG_CORRUPT (d_out_len[i] = 0): a
+ * size word above the block maximum, input that ends early, a block that does
+ * not decode, a checksum mismatch, decoded length != content size, output
+ * past the capacity when no content size is given.  A block is judged as the
+ * block decoder above judges it, with capacity equal to the block's decoded
+ * length (the sequence whose literals end at the block's last byte ends it);
+ * offset 0 is rejected; with linked blocks (B.Indep 0) an offset may reach
+ * into the earlier blocks' output, as far as the frame has produced.  Every
+ * frame this accepts liblz4 accepts with the same bytes; liblz4 also accepts a
+ * few this rejects, because it applies the block end rule against a larger
+ * capacity.  On FSG_OK d_out_len[i] is the decoded length.
+ *
+ * Routes.  Frames with independent blocks and a content size within the
+ * capacity take the fast route: every block but the last is taken to be full,
+ * so block k decodes to min(block size, size - k * block size) bytes at
+ * k * block size, all blocks of the batch side by side on the block decoder.
+ * Linked blocks, frames without a content size, and every frame the fast route
+ * does not accept (a short block in the middle, a block that fails) go to a
+ * serial decoder, one lane per message, which alone decides their verdict:
+ * correct and slow.  The lz4 command's default output is such a frame.
+ *
+ * "What a *_batch call writes" holds for both calls, every status and route.
+ * Slots: fsg_lz4f_max_frame_length(d_in_len[i], id) for compress. */
+
+/* n + 4 * ceil(n / block size) + 23: descriptor (15), a size word per block,
+ * the bytes (a block that does not shrink is stored raw), end mark (4),
+ * content checksum (4).  LZ4F_compressFrameBound gives 4 more (it counts the
+ * largest descriptor, 19 bytes with a DictID).  0 for an id outside 4..7. */
+size_t fsg_lz4f_max_frame_length(size_t n, uint32_t block_size_id);
+
+/* Workspace of fsg_lz4f_compress_batch for a batch of n_msgs messages and
+ * total_in_bytes input bytes in all: block columns and the block encoder's
+ * workspace (16 KiB of position table) for n_msgs + total_in_bytes / block
+ * size blocks, and staging for the encoded blocks.  The call takes no input
+ * size: it reads from workspace_bytes what the workspace was sized for.
+ * Messages whose blocks do not fit a workspace sized for fewer bytes get
+ * FSG_CORRUPT with d_out_len 0 (nothing else changes). */
+size_t fsg_lz4f_compress_workspace_bytes(uint32_t n_msgs, uint64_t total_in_bytes, uint32_t block_size_id);
+
+/* Batched frame compress, columns as fsg_lz4_compress_batch.  flags bit 0:
+ * write a content checksum.  The blocks go through the block encoders of
+ * fsg_lz4_compress_batch with that call's routing; option lz4f_block_wave_min
+ * (FSG_L4F_BLOCK_WAVE_MIN) is their wave threshold, -1 (default) the
+ * automatic rule applied to the workspace's block entries.  A NULL workspace
+ * or one below fsg_lz4f_compress_workspace_bytes(n_msgs, 0, id) is
+ * FSG_ERR_INVALID_ARG; n_msgs == 0 succeeds and launches nothing. */
+int fsg_lz4f_compress_batch(const uint8_t *d_in, const uint64_t *d_in_off,
+                            const uint32_t *d_in_len, uint32_t n_msgs,
+                            uint8_t *d_out, const uint64_t *d_out_off,
+                            uint32_t *d_out_len, int32_t *d_status,
+                            uint32_t block_size_id, uint32_t flags,
+                            void *d_workspace, size_t workspace_bytes,
+                            void *stream);
+
+/* Workspace of fsg_lz4f_decompress_batch: block columns for n_msgs +
+ * total_in_bytes / 256 blocks (a full 64 KiB block has at least 257 bytes),
+ * staging for the blocks, and the block decoder's workspace.  A workspace
+ * sized for fewer bytes never changes bytes or statuses: frames whose blocks
+ * do not fit go to the serial decoder, blocks whose bitmap does not fit to the
+ * block decoder's one-pass kernel. */
+size_t fsg_lz4f_decompress_workspace_bytes(uint32_t n_msgs, uint64_t total_in_bytes);
+
+/* Batched frame decompress, columns as fsg_lz4_decompress_batch_ws.  Option
+ * lz4f_force_serial (FSG_L4F_FORCE_SERIAL) = 1 sends every frame to the serial
+ * decoder.  A NULL workspace or one below
+ * fsg_lz4f_decompress_workspace_bytes(n_msgs, 0) is FSG_ERR_INVALID_ARG;
+ * n_msgs == 0 succeeds and launches nothing. */
+int fsg_lz4f_decompress_batch(const uint8_t *d_in, const uint64_t *d_in_off,
+                              const uint32_t *d_in_len, uint32_t n_msgs,
+                              uint8_t *d_out, const uint64_t *d_out_off,
+                              const uint32_t *d_out_cap, uint32_t *d_out_len,
+                              int32_t *d_status, void *d_workspace,
+                              size_t workspace_bytes, void *stream);
+
+/* The content size each body's descriptor states, for sizing slots
+ * (fsg_uncompressed_lengths_batch's counterpart): d_content_size[i] = the
+ * size, or FSG_LZ4F_NO_CONTENT_SIZE when the frame states none or the
+ * descriptor is bad; d_status[i] = FSG_OK or FSG_BAD_HEADER. */
+#define FSG_LZ4F_NO_CONTENT_SIZE 0xFFFFFFFFFFFFFFFFull
+int fsg_lz4f_content_sizes_batch(const uint8_t *d_in, const uint64_t *d_in_off,
+                                 const uint32_t *d_in_len, uint32_t n_msgs,
+                                 uint64_t *d_content_size, int32_t *d_status,
+                                 void *stream);
+
+/* Path reports ("Path reports" in flare_snappy_gpu.h: host code, from a host
+ * copy of the workspace's first 256 bytes taken after the call completed,
+ * asked with the call's n_msgs, workspace_bytes and block size id). */
+struct fsg_lz4f_encode_report {
+  uint64_t blocks;             /* blocks encoded */
+  uint64_t raw_blocks;         /* of them stored raw */
+  uint64_t overflow_messages;  /* messages that did not fit the workspace (FSG_CORRUPT) */
+  uint64_t block_entries;      /* blocks the workspace holds */
+  uint64_t block_wave_min;     /* wave threshold of the block encode (0xFFFFFFFF: none) */
+};
+int fsg_lz4f_compress_report(const void *header_host_copy, uint32_t n_msgs,
+                             size_t workspace_bytes, uint32_t block_size_id,
+                             struct fsg_lz4f_encode_report *out);
+
+struct fsg_lz4f_decode_report {
+  uint64_t fast_messages;      /* answered by the fast route (FSG_OK) */
+  uint64_t fast_blocks;        /* their blocks */
+  uint64_t empty_messages;     /* frames without blocks, finished by the index pass */
+  uint64_t serial_linked;      /* serial route: linked blocks */
+  uint64_t serial_no_size;     /* serial route: no content size */
+  uint64_t serial_rejected;    /* serial route: the fast route did not accept the frame */
+  uint64_t serial_forced;      /* serial route: option lz4f_force_serial */
+  uint64_t checksummed_units;  /* block and content checksums computed */
+  uint64_t inner_fallback_blocks; /* blocks the block decoder's one-pass kernel finished */
+  uint64_t block_entries;      /* blocks the workspace holds */
+};
+int fsg_lz4f_decompress_report(const void *header_host_copy, uint32_t n_msgs,
+                               size_t workspace_bytes,
+                               struct fsg_lz4f_decode_report *out);
+
 #ifdef __cplusplus
 }
 #endif

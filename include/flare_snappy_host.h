@@ -108,6 +108,15 @@ size_t fsh_cpu_lz4_compress(const uint8_t* in, size_t n, uint8_t* out);
 int fsh_cpu_lz4_uncompress(const uint8_t* in, size_t n, uint8_t* out, size_t cap, uint32_t* ulen);
 /* registers the LZ4 CompressHandler (host/lz4_compress.h); 0 on success */
 int fsh_register_lz4(void);
+/* ---- LZ4 frames (LZ4 Frame Format 1.6.x; include/flare_lz4_gpu.h, "LZ4
+ * frames"): the host codec, same bytes and verdicts as the GPU calls. */
+/* n + 4 * ceil(n / block size) + 23 (0 for a block size id outside 4..7) */
+size_t fsh_lz4f_max_frame_length(size_t n, int block_size_id);
+/* frame of n bytes into out; its length (0 for a bad block size id) */
+size_t fsh_cpu_lz4f_compress(const uint8_t* in, size_t n, uint8_t* out, int block_size_id, int content_checksum);
+/* frame to out (cap bytes): 1 ok, 0 corrupt, -1 bad header, -2 content size
+ * above cap; *out_len = decoded length (ok) or min(content size, 2^32-1) (-2) */
+int fsh_cpu_lz4f_uncompress(const uint8_t* in, size_t n, uint8_t* out, size_t cap, uint32_t* out_len);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,140 @@
+"""LZ4 frames beside the single-block LZ4 bodies, device-resident: the same
+text bodies through fsg_lz4f_compress_batch / fsg_lz4f_decompress_batch and
+through fsg_lz4_compress_batch / fsg_lz4_decompress_batch_ws in one process,
+the two alternating launch by launch, each launch timed with HIP events on the
+launch stream after warm-up launches of both; the median, minimum and maximum
+per call.  One JSON line per row.
+
+    python tools/lz4f_bench.py [--rows 16x4m,c3] [--launches 7] [--warmup 2] [--bid 4]
+
+Rows: 16x4m (16 x 4 MiB: 64 independent blocks a body, where the format adds
+parallelism) and c3 (65,536 x 64 KiB: one block a body, the cost of the plan,
+stage, assemble and finish passes).  Round trips are checked untimed, frames of
+a sample against the frame oracle.  `staging_bytes`: what the decompressor's
+stage pass copies (one read and one write of the compressed blocks).
+"""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import numpy as np
+
+REPO = Path(__file__).resolve().parents[1]
+for p in (REPO / "flare-cpp_amd" / "py", REPO / "oracle", REPO / "tests"):
+    sys.path.insert(0, str(p))
+import fsg  # noqa: E402
+
+ROWS = {"16x4m": (16, 4 << 20), "c3": (65536, 64 << 10), "256x256k": (256, 256 << 10)}
+
+
+def stats(ms):
+    return {"median_ms": round(float(np.median(ms)), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+
+
+def alternate(torch, s, fns, warmup, launches):
+    """Times each of `fns` launches times, alternating them, after `warmup`
+    untimed rounds of all."""
+    ms = [[] for _ in fns]
+    for k in range(warmup + launches):
+        for i, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            fn()
+            e1.record(s)
+            torch.cuda.synchronize()
+            if k >= warmup:
+                ms[i].append(e0.elapsed_time(e1))
+    return [stats(m) for m in ms]
+
+
+def row(torch, codec, name, bid, warmup, launches):
+    dev = torch.device("cuda", 0)
+    lib = codec.lib
+    n, size = ROWS[name]
+    batch = fsg.make_batch(fsg.KIND_TEXT, np.full(n, size, np.uint32))
+    raw = batch.total
+    H = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    s = torch.cuda.current_stream()
+    d_raw, d_ro, d_rl = H(batch.data), H(batch.offsets), H(batch.lens)
+    # single-block bodies
+    b_off, b_tot = fsg.slot_offsets(np.array([lib.fsg_lz4_max_compressed_length(int(x)) for x in batch.lens], np.uint64))
+    d_b, d_bo = torch.zeros(b_tot, dtype=torch.uint8, device=dev), H(b_off)
+    d_bl = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_bst = torch.zeros(n, dtype=torch.int32, device=dev)
+    b_ws = codec.lz4_compress_workspace(n)
+    # frames
+    f_off, f_tot = fsg.slot_offsets(np.array([lib.fsg_lz4f_max_frame_length(int(x), bid) for x in batch.lens], np.uint64))
+    d_f, d_fo = torch.zeros(f_tot, dtype=torch.uint8, device=dev), H(f_off)
+    d_fl = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_fst = torch.zeros(n, dtype=torch.int32, device=dev)
+    f_ws = codec.lz4f_compress_workspace(n, raw, bid)
+
+    def enc_block():
+        codec.lz4_compress(d_raw, d_ro, d_rl, n, d_b, d_bo, d_bl, d_bst, b_ws, stream=s)
+
+    def enc_frame():
+        codec.lz4f_compress(d_raw, d_ro, d_rl, n, d_f, d_fo, d_fl, d_fst, f_ws, block_size_id=bid, stream=s)
+
+    enc = alternate(torch, s, (enc_block, enc_frame), warmup, launches)
+    enc_rep = codec.lz4f_compress_report(f_ws, n, bid)
+    body_bytes = int(d_bl.cpu().numpy().view(np.uint32).astype(np.uint64).sum())
+    frame_len = d_fl.cpu().numpy().view(np.uint32)
+    frame_bytes = int(frame_len.astype(np.uint64).sum())
+    enc_ok = int((d_bst != 0).sum().item()) == 0 and int((d_fst != 0).sum().item()) == 0
+    from bind import Lz4Oracle
+    import lz4f_ref
+    o = Lz4Oracle()
+    host_f = d_f.cpu().numpy()
+    sample_ok = all(host_f[int(f_off[i]):int(f_off[i]) + int(frame_len[i])].tobytes() ==
+                    lz4f_ref.compress_frame(o, batch.item(int(i)), bid)
+                    for i in np.linspace(0, n - 1, 8).astype(np.int64))
+    del b_ws, f_ws, host_f
+    torch.cuda.empty_cache()
+    # decode: both into slots of the input layout
+    d_out_b = torch.full((raw,), 0xA5, dtype=torch.uint8, device=dev)
+    d_out_f = torch.full((raw,), 0xA5, dtype=torch.uint8, device=dev)
+    d_ol = torch.zeros(n, dtype=torch.int32, device=dev)
+    bd_ws = codec.lz4_decompress_workspace(n, int(b_tot))
+    fd_ws = codec.lz4f_decompress_workspace(n, frame_bytes)  # sized for the frames' bytes, as a caller would
+
+    def dec_block():
+        codec.lz4_decompress(d_b, d_bo, d_bl, n, d_out_b, d_ro, d_rl, d_ol, d_bst, stream=s, workspace=bd_ws)
+
+    def dec_frame():
+        codec.lz4f_decompress(d_f, d_fo, d_fl, n, d_out_f, d_ro, d_rl, d_ol, d_fst, fd_ws, stream=s)
+
+    dec = alternate(torch, s, (dec_block, dec_frame), warmup, launches)
+    dec_rep = codec.lz4f_decompress_report(fd_ws, n)
+    dec_ok = (int((d_bst != 0).sum().item()) == 0 and int((d_fst != 0).sum().item()) == 0 and
+              bool(torch.equal(d_out_b, d_raw)) and bool(torch.equal(d_out_f, d_raw)))
+    out = {"row": name, "n": n, "size": size, "block_size_id": bid, "launches": launches, "warmup": warmup,
+           "raw_bytes": raw, "body_bytes": body_bytes, "frame_bytes": frame_bytes,
+           "ratio_bodies": round(raw / body_bytes, 4), "ratio_frames": round(raw / frame_bytes, 4),
+           "compress_block_call": enc[0], "compress_frame_call": enc[1],
+           "compress_gain": round(enc[0]["median_ms"] / enc[1]["median_ms"], 3),
+           "decompress_block_call": dec[0], "decompress_frame_call": dec[1],
+           "decompress_gain": round(dec[0]["median_ms"] / dec[1]["median_ms"], 3),
+           "staging_bytes": frame_bytes, "compress_report": enc_rep, "decompress_report": dec_rep,
+           "status_ok": enc_ok, "frames_equal_oracle_sample": sample_ok, "roundtrip_ok": dec_ok}
+    print(json.dumps(out), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", default="16x4m,c3")
+    ap.add_argument("--bid", type=int, default=4, help="block size id 4..7")
+    ap.add_argument("--launches", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    a = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("lz4f_bench needs a GPU")
+    codec = fsg.SnappyGPU(0)
+    for name in a.rows.split(","):
+        row(torch, codec, name, a.bid, a.warmup, a.launches)
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
