@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/flare_snappy_gpu.h"
+#include "batch_plan.h"
 #include "pinned.h"
 #include "snappy_cpu.h"
 
@@ -23,14 +24,17 @@ namespace flare::gpu {
 
 namespace {
 
-struct DevBuf {
+// A grow-only buffer: device memory, or pinned host memory (so
+// hipMemcpyAsync is a true DMA).
+template <bool kPinned>
+struct Buf {
   void* p = nullptr;
   size_t cap = 0;
   bool reserve(size_t n) {
     if (n <= cap) return true;
     release();
     size_t want = n + n / 4 + 4096;
-    if (hipMalloc(&p, want) != hipSuccess) {
+    if ((kPinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want)) != hipSuccess) {
       p = nullptr;
       return false;
     }
@@ -38,38 +42,15 @@ struct DevBuf {
     return true;
   }
   void release() {
-    if (p) (void)hipFree(p);
+    if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
     p = nullptr;
     cap = 0;
   }
   template <class T>
   T* as() const { return static_cast<T*>(p); }
 };
-
-struct HostBuf {  // pinned host memory, so hipMemcpyAsync is a true DMA
-  void* p = nullptr;
-  size_t cap = 0;
-  bool reserve(size_t n) {
-    if (n <= cap) return true;
-    release();
-    size_t want = n + n / 4 + 4096;
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
-      p = nullptr;
-      return false;
-    }
-    cap = want;
-    return true;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
-enum Kind { kCompress = 0, kDecompress = 1, kValidate = 2 };
+using DevBuf = Buf<false>;
+using HostBuf = Buf<true>;
 
 struct Request {
   const cord_buf* in;
@@ -81,8 +62,6 @@ struct Request {
   void* latch = nullptr;
   void (*signal)(void*) = nullptr;
 };
-
-inline size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
 
 // Host threads for gather / scatter of large chunks (copies into pinned
 // staging are CPU memcpy; one core moves ~10 GB/s).
@@ -123,11 +102,6 @@ const uint8_t* flatten(const cord_buf& in, std::vector<uint8_t>* tmp) {
   return tmp->data();
 }
 
-// A valid stream expands at most 64/3x (a 3-byte COPY_2 of length 64) plus
-// its header: a longer header length cannot decode (the reference would run
-// out of input and return false), so nothing is allocated for it.
-inline bool plausible_length(uint32_t ulen, size_t in_len) { return (uint64_t)ulen <= 22ull * in_len + 64; }
-
 bool cpu_run(Kind kind, const cord_buf& in, cord_buf* out) {
   std::vector<uint8_t> tin, tout;  // per call: no thread_local (see snappy_cpu.cc)
   const uint8_t* p = flatten(in, &tin);
@@ -157,6 +131,72 @@ struct Counters {
       failures{0}, cpu_messages{0}, fallbacks{0}, adopted{0}, d2h_bytes{0}, packed_chunks{0},
       device_fallback_messages{0}, device_single_pass_messages{0}, device_fallback_batches{0};
 };
+
+static_assert(FSG_OK == kStatusOk, "batch_plan.h's packed_layout tests the device's status");
+
+// What a slot's batch call was given (path report: its workspace's header
+// follows the results down on the same stream when it had a workspace).
+struct CallArgs {
+  uint32_t n = 0, max_len = 0;
+  size_t ws_bytes = 0;  // 0: no workspace
+};
+
+// Chunk k of a batch: bodies [a, b) on stream `slot`, input bytes [ia, ib)
+// of the staging buffers, output slots [oa, ob).
+struct Chunk {
+  size_t k;
+  int slot;
+  uint32_t a, b, cn;
+  size_t ia, ib, oa, ob;
+  uint64_t staged = 0, direct = 0;  // gather_chunk: input bytes staged / left to the device gather
+};
+
+// One device batch: what the stages of Device::run share.
+struct Batch {
+  const std::vector<Request*>& reqs;
+  const Kind kind;
+  const uint32_t n;
+  BatchPlan plan;
+  MetaColumns h{}, d{};  // host (pinned) and device metadata columns
+  GatherColumns hg{}, dg{};
+  // The unpacked chunks' D2H target: a pinned slab the outputs are adopted
+  // from, else staging.
+  OutSlab* slab = nullptr;
+  bool adopt = false;
+  uint8_t* hout = nullptr;
+  bool failed = false;
+  int pending[kSlots];  // chunk in flight on each stream
+  CallArgs call[kSlots];
+  std::vector<uint64_t> poff;  // a packed chunk's offsets (packed_layout)
+  uint64_t bytes_in = 0, bytes_out = 0, adopted = 0, corrupt = 0, d2h = 0, packed_chunks = 0;
+  uint64_t fb_messages = 0, fb_batches = 0, single_pass = 0;
+
+  Batch(const std::vector<Request*>& r, Kind k) : reqs(r), kind(k), n((uint32_t)r.size()) {
+    std::fill(pending, pending + kSlots, -1);
+  }
+  bool compress() const { return kind == kCompress; }
+  bool validate() const { return kind == kValidate; }
+  Chunk chunk(size_t k) const {
+    const uint32_t a = plan.cut[k], b = plan.cut[k + 1];
+    return Chunk{k, (int)(k % kSlots), a, b, b - a, plan.in_begin(k), plan.in_end(k), plan.out_begin(k),
+                 plan.out_end(k)};
+  }
+};
+
+// What the plan needs of each request: sizes, and for decode kinds the
+// length header's verdict.
+std::vector<PlanBody> plan_bodies(const std::vector<Request*>& reqs, Kind kind) {
+  std::vector<PlanBody> bodies(reqs.size());
+  for (size_t i = 0; i < reqs.size(); ++i) {
+    const cord_buf& in = *reqs[i]->in;
+    bodies[i] = PlanBody{in.size(), (uint32_t)in.backing_block_num(), 0, true};
+    if (kind == kCompress) continue;
+    uint8_t hdr[5];
+    const size_t k = in.copy_to(hdr, sizeof(hdr));
+    bodies[i].header_ok = fsg_get_uncompressed_length(hdr, k, &bodies[i].ulen, /*lenient=*/1) != 0;
+  }
+  return bodies;
+}
 
 // One HIP device's runtime.
 struct Device {
@@ -210,20 +250,10 @@ struct Device {
         (void)hipStreamDestroy(st);
         st = nullptr;
       }
-    d_in.release();
-    d_meta.release();
-    d_out.release();
-    d_gath.release();
-    for (auto& w : d_ws) w.release();
-    for (auto& w : d_pack) w.release();
-    for (auto& w : d_pmeta) w.release();
-    h_total.release();
-    h_pack.release();
-    h_rep.release();
-    h_in.release();
-    h_meta.release();
-    h_out.release();
-    h_gath.release();
+    for (DevBuf* b : {&d_in, &d_meta, &d_out, &d_gath}) b->release();
+    for (auto* per_slot : {d_ws, d_pack, d_pmeta})
+      for (int s = 0; s < kSlots; ++s) per_slot[s].release();
+    for (HostBuf* b : {&h_total, &h_pack, &h_rep, &h_in, &h_meta, &h_out, &h_gath}) b->release();
     id = -1;
   }
 
@@ -231,394 +261,351 @@ struct Device {
   // finishes gets handled = true; returns false after a device error (the
   // unfinished requests are left to the host codec).
   bool run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr);
+
+  // run's stages, in a chunk's order.  A stage that returns false has
+  // reported the error; the batch has then failed.
+  bool reserve(Batch& bt);
+  void gather_chunk(Batch& bt, Chunk* c);
+  bool upload_chunk(Batch& bt, const Chunk& c);
+  bool launch_chunk(Batch& bt, const Chunk& c);
+  bool download_chunk(Batch& bt, const Chunk& c);
+  void finish_chunk(Batch& bt, int slot);
+  void read_report(Batch& bt, int slot);
+  void drain(Batch& bt);
+  static void add_counters(const Batch& bt, Counters* ctr);
 };
 
 std::atomic<int> g_inject_errors{0};  // test hook: fail the next n device batches
 
 bool Device::run(const std::vector<Request*>& reqs, Kind kind, Counters* ctr) {
-  const uint32_t n = (uint32_t)reqs.size();
-  if (n == 0) return true;
+  if (reqs.empty()) return true;
   for (int k = g_inject_errors.load(); k > 0;)
     if (g_inject_errors.compare_exchange_weak(k, k - 1)) return false;
   if (hipSetDevice(id) != hipSuccess) return false;
-  const bool compress = kind == kCompress, validate = kind == kValidate;
-  // ---- sizes; messages whose verdict the header already decides are skipped
-  std::vector<uint32_t> ulen(n, 0);
-  std::vector<uint8_t> skip(n, 0);
-  std::vector<uint32_t> blk_base(n + 1, 0);
-  size_t total_out = 0;
-  uint32_t max_len = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    const size_t len = reqs[i]->in->size();
-    blk_base[i + 1] = blk_base[i];
-    // beyond the format's uint32 lengths, or (compress) a worst-case output
-    // the u32 slot sizes cannot describe: the host codec takes these
-    if (len > 0xffffffffu || (compress && fsg_max_compressed_length(len) > 0xffffffffu)) {
-      skip[i] = 2;
-      continue;
+  Batch bt(reqs, kind);
+  bt.plan = plan_batch(kind, plan_bodies(reqs, kind).data(), bt.n,
+                       bt.compress() ? chunk_bytes_compress : chunk_bytes, pack_min_bytes);
+  if (!reserve(bt)) return false;
+  for (size_t k = 0; k < bt.plan.n_chunks(); ++k) {
+    Chunk c = bt.chunk(k);
+    finish_chunk(bt, c.slot);  // its previous chunk (staging regions are disjoint, streams are not)
+    if (bt.failed) break;
+    gather_chunk(bt, &c);
+    if (!upload_chunk(bt, c) || !launch_chunk(bt, c) || !download_chunk(bt, c)) {
+      bt.failed = true;
+      break;
     }
-    if (compress) {
-      total_out += align16(fsg_max_compressed_length(len));
-      max_len = std::max<uint32_t>(max_len, (uint32_t)len);
-    } else {
-      uint8_t hdr[5];
-      const size_t k = reqs[i]->in->copy_to(hdr, sizeof(hdr));
-      uint32_t u = 0;
-      if (fsg_get_uncompressed_length(hdr, k, &u, /*lenient=*/1) == 0 || !plausible_length(u, len)) {
-        skip[i] = 1;  // the reference returns false
-        continue;
-      }
-      ulen[i] = u;
-      if (!validate) total_out += align16(u);
-    }
-    blk_base[i + 1] += (uint32_t)reqs[i]->in->backing_block_num();
+    bt.pending[c.slot] = (int)k;
   }
-  const uint32_t n_blk = blk_base[n];
-  // metadata: in_off u64, out_off u64, in_len u32, out_cap u32, out_len u32, status i32
-  const size_t meta_bytes = (size_t)n * (8 + 8 + 4 + 4 + 4 + 4);
-  const size_t gath_bytes = (size_t)n_blk * (8 + 8 + 4);
-  size_t total_in = 0;
-  for (uint32_t i = 0; i < n; ++i)
-    if (!skip[i]) total_in += align16(reqs[i]->in->size());
-  if (!h_in.reserve(total_in + 16) || !h_meta.reserve(meta_bytes) || !h_gath.reserve(gath_bytes + 16) ||
-      !d_in.reserve(total_in + 16) || !d_meta.reserve(meta_bytes) || !d_gath.reserve(gath_bytes + 16) ||
-      !d_out.reserve(total_out + 16) || !h_rep.reserve(kSlots * fsg_report_header_bytes()))
+  drain(bt);
+  if (bt.slab) OutSlabRelease(bt.slab);  // the adopted ranges keep it alive
+  add_counters(bt, ctr);
+  return !bt.failed;
+}
+
+// The batch's buffers, its column views with the plan's columns in them, and
+// the unpacked chunks' D2H target.  False (nothing held) when memory is short.
+bool Device::reserve(Batch& bt) {
+  const BatchPlan& p = bt.plan;
+  const size_t n = bt.n;
+  if (!h_in.reserve(p.total_in + 16) || !h_meta.reserve(p.meta_bytes) || !h_gath.reserve(p.gath_bytes + 16) ||
+      !d_in.reserve(p.total_in + 16) || !d_meta.reserve(p.meta_bytes) || !d_gath.reserve(p.gath_bytes + 16) ||
+      !d_out.reserve(p.total_out + 16) || !h_rep.reserve(kSlots * fsg_report_header_bytes()))
     return false;
-
-  // Metadata columns, back to back in this order on host and device (the
-  // one-chunk path below copies in_off..out_cap and out_len..status as two
-  // contiguous spans, so the order and the packing are load-bearing):
-  //   in_off u64[n] | out_off u64[n] | in_len u32[n] | out_cap u32[n] | out_len u32[n] | status i32[n]
-  constexpr size_t kColInOff = 0, kColOutOff = 8, kColInLen = 16, kColOutCap = 20, kColOutLen = 24, kColStatus = 28;
-  static_assert(kColOutOff == kColInOff + 8 && kColInLen == kColOutOff + 8 && kColOutCap == kColInLen + 4 &&
-                    kColOutLen == kColOutCap + 4 && kColStatus == kColOutLen + 4,
-                "the combined H2D (24n bytes from in_off) and D2H (8n bytes from out_len) copies need these "
-                "columns contiguous and in this order");
-  uint8_t* m = h_meta.as<uint8_t>();
-  auto* in_off = reinterpret_cast<uint64_t*>(m + kColInOff * n);
-  auto* out_off = reinterpret_cast<uint64_t*>(m + kColOutOff * n);
-  auto* in_len = reinterpret_cast<uint32_t*>(m + kColInLen * n);
-  auto* out_cap = reinterpret_cast<uint32_t*>(m + kColOutCap * n);
-  auto* out_len = reinterpret_cast<uint32_t*>(m + kColOutLen * n);
-  auto* status = reinterpret_cast<int32_t*>(m + kColStatus * n);
-  uint8_t* dm = d_meta.as<uint8_t>();
-  auto* d_in_off = reinterpret_cast<uint64_t*>(dm + kColInOff * n);
-  auto* d_out_off = reinterpret_cast<uint64_t*>(dm + kColOutOff * n);
-  auto* d_in_len = reinterpret_cast<uint32_t*>(dm + kColInLen * n);
-  auto* d_out_cap = reinterpret_cast<uint32_t*>(dm + kColOutCap * n);
-  auto* d_out_len = reinterpret_cast<uint32_t*>(dm + kColOutLen * n);
-  auto* d_status = reinterpret_cast<int32_t*>(dm + kColStatus * n);
-  // pinned-block descriptors: src u64, dst offset u64, length u32 (0 = staged)
-  uint8_t* g = h_gath.as<uint8_t>();
-  auto* g_src = reinterpret_cast<uint64_t*>(g);
-  auto* g_dst = reinterpret_cast<uint64_t*>(g + 8ull * n_blk);
-  auto* g_len = reinterpret_cast<uint32_t*>(g + 16ull * n_blk);
-  uint8_t* dg = d_gath.as<uint8_t>();
-  auto* dg_src = reinterpret_cast<uint64_t*>(dg);
-  auto* dg_dst = reinterpret_cast<uint64_t*>(dg + 8ull * n_blk);
-  auto* dg_len = reinterpret_cast<uint32_t*>(dg + 16ull * n_blk);
-  uint8_t* hin = h_in.as<uint8_t>();
-
-  // ---- layout (offsets only; the copies happen per chunk)
-  size_t pos_in = 0, pos_out = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    in_off[i] = pos_in;
-    out_off[i] = pos_out;
-    if (skip[i]) {
-      in_len[i] = 0;
-      out_cap[i] = 0;
-      continue;
-    }
-    const size_t w = reqs[i]->in->size();
-    in_len[i] = (uint32_t)w;
-    pos_in += align16(w);
-    const size_t cap = compress ? fsg_max_compressed_length(w) : (validate ? 0 : ulen[i]);
-    out_cap[i] = (uint32_t)cap;
-    pos_out += align16(cap);
-  }
-  // ---- chunks: [first, end) message ranges of >= chunk_bytes input
-  std::vector<uint32_t> cut{0};
-  const size_t cbytes = compress ? chunk_bytes_compress : chunk_bytes;
-  for (uint32_t i = 0; i < n; ++i)
-    if (i + 1 < n && in_off[i + 1] - in_off[cut.back()] >= cbytes) cut.push_back(i + 1);
-  cut.push_back(n);
-  const size_t n_chunks = cut.size() - 1;
-  // ---- which chunks pack their outputs on the device.  The others download
-  // their slot ranges, back to back in chunk order (hbase), into one D2H
-  // target: a pinned slab the outputs are adopted from, else staging.  A
-  // packed chunk gets a slab of its own once its total is known.
-  std::vector<uint8_t> packed(n_chunks, 0);
-  std::vector<size_t> hbase(n_chunks, 0);
-  size_t host_out = 0;
-  bool any_packed = false, any_unpacked = false;
-  for (size_t k = 0; k < n_chunks; ++k) {
-    const size_t oa = out_off[cut[k]], ob = cut[k + 1] < n ? out_off[cut[k + 1]] : pos_out;
-    if (compress && ob > oa && ob - oa >= pack_min_bytes) {
-      packed[k] = 1;
-      any_packed = true;
-    } else {
-      hbase[k] = host_out;
-      host_out += ob - oa;
-      any_unpacked = true;
-    }
-  }
-  if (any_packed && !h_total.reserve(kSlots * sizeof(uint64_t))) return false;
-  OutSlab* slab = validate || !any_unpacked ? nullptr : AcquireOutSlab(host_out + 16);
+  bt.h = MetaColumns::at(h_meta.p, n);
+  bt.d = MetaColumns::at(d_meta.p, n);
+  bt.hg = GatherColumns::at(h_gath.p, p.blk_base[n]);
+  bt.dg = GatherColumns::at(d_gath.p, p.blk_base[n]);
+  memcpy(bt.h.in_off, p.in_off.data(), 8 * n);
+  memcpy(bt.h.out_off, p.out_off.data(), 8 * n);
+  memcpy(bt.h.in_len, p.in_len.data(), 4 * n);
+  memcpy(bt.h.out_cap, p.out_cap.data(), 4 * n);
+  if (p.any_packed && !h_total.reserve(kSlots * sizeof(uint64_t))) return false;
+  bt.slab = bt.validate() || !p.any_unpacked ? nullptr : AcquireOutSlab(p.host_out + 16);
   // under slab pressure outputs are copied, so this slab returns to the pool
   // right after the batch instead of being held by long-lived cord_bufs
-  const bool adopt = slab && !OutSlabsUnderPressure();
-  if (!validate && any_unpacked && slab == nullptr && !h_out.reserve(host_out + 16)) return false;
-  uint8_t* hout = slab ? OutSlabData(slab) : h_out.as<uint8_t>();
+  bt.adopt = bt.slab && !OutSlabsUnderPressure();
+  if (!bt.validate() && p.any_unpacked && bt.slab == nullptr && !h_out.reserve(p.host_out + 16)) return false;
+  bt.hout = bt.slab ? OutSlabData(bt.slab) : h_out.as<uint8_t>();
+  return true;
+}
 
-  bool failed = false;
-  std::vector<int> pending(kSlots, -1);  // chunk in flight on each stream
-  uint64_t bytes_in = 0, bytes_out = 0, adopted = 0, corrupt = 0, d2h = 0, packed_chunks = 0;
-  std::vector<uint64_t> poff;  // a packed chunk's offsets, by fsg_pack_batch's rule
-  // Path report: what each slot's batch call was given (its workspace's header
-  // follows the results down on the same stream when it had a workspace)
-  struct CallArgs {
-    uint32_t n = 0, max_len = 0;
-    size_t ws_bytes = 0;  // 0: no workspace
-  } call[kSlots];
-  const size_t rep_bytes = fsg_report_header_bytes();
-  uint64_t fb_messages = 0, fb_batches = 0, single_pass = 0;
-  auto read_report = [&](int slot) {
-    const void* hdr = call[slot].ws_bytes ? h_rep.as<uint8_t>() + rep_bytes * slot : nullptr;
-    uint64_t fb = 0, sp = 0;
-    if (compress) {
-      fsg_encode_report r;
-      if (fsg_compress_report(hdr, call[slot].n, call[slot].max_len, call[slot].ws_bytes, &r) != FSG_SUCCESS) return;
-      fb = r.fallback_messages;
-      sp = r.no_workspace_messages;
-    } else {
-      fsg_decode_report r;
-      if (fsg_decompress_report(hdr, call[slot].n, call[slot].ws_bytes, validate ? FSG_FLAG_VALIDATE_ONLY : 0u,
-                                &r) != FSG_SUCCESS)
-        return;
-      fb = r.fallback_messages;
-      // validate-only is single-pass by design
-      sp = r.path == FSG_PATH_NO_WORKSPACE || r.path == FSG_PATH_FORCED ? r.single_pass_messages : 0;
+// cord_buf backing blocks (cord_buf.cc:1469-1475): pinned ones become
+// descriptors for the device gather, the rest is staged.
+void Device::gather_chunk(Batch& bt, Chunk* c) {
+  const BatchPlan& p = bt.plan;
+  const GatherColumns g = bt.hg;
+  uint8_t* hin = h_in.as<uint8_t>();
+  // The host threads add to these once per body.  Each fills a cache line of
+  // its own, so the adds do not take away the line that holds the pointers
+  // every block reads (16,384 x 64 KiB from pinned blocks, compress: 101-103
+  // ms, against 105-110 with the two sums next to those pointers; DESIGN.md
+  // section 5, "Host batch plan").
+  struct alignas(64) Sum {
+    std::atomic<uint64_t> v{0};
+  } staged, direct;
+  parallel_for(c->a, c->b, c->ib - c->ia, [&](uint32_t i) {
+    if (p.skip[i]) return;
+    const cord_buf& in = *bt.reqs[i]->in;
+    size_t w = 0;
+    uint64_t st = 0, dr = 0;
+    for (size_t blk = 0; blk < in.backing_block_num(); ++blk) {
+      std::string_view v = in.backing_block(blk);
+      const uint32_t j = p.blk_base[i] + (uint32_t)blk;
+      g.dst[j] = p.in_off[i] + w;
+      if (v.size() >= 1024 && IsPinned(v.data(), v.size())) {
+        g.src[j] = reinterpret_cast<uint64_t>(v.data());
+        g.len[j] = (uint32_t)v.size();
+        dr += v.size();
+      } else {
+        g.src[j] = 0;
+        g.len[j] = 0;
+        memcpy(hin + p.in_off[i] + w, v.data(), v.size());
+        st += v.size();
+      }
+      w += v.size();
     }
-    fb_messages += fb;
-    fb_batches += fb ? 1 : 0;
-    single_pass += sp;
-  };
-  auto finish = [&](int slot) {  // wait for a slot's chunk, scatter its results
-    const int k = pending[slot];
-    if (k < 0) return;
-    pending[slot] = -1;
-    if (hipStreamSynchronize(streams[slot]) != hipSuccess) {
-      fprintf(stderr, "[flare-snappy-gpu] stream error on device %d\n", id);
-      failed = true;
+    staged.v += st;
+    direct.v += dr;
+  });
+  c->staged = staged.v.load();
+  c->direct = direct.v.load();
+}
+
+// H2D: the staged input, the descriptors and the device gather, the columns.
+bool Device::upload_chunk(Batch& bt, const Chunk& c) {
+  const BatchPlan& p = bt.plan;
+  const MetaColumns &h = bt.h, &d = bt.d;
+  const GatherColumns &hg = bt.hg, &dg = bt.dg;
+  hipStream_t st = streams[c.slot];
+  bool ok = true;
+  if (c.staged && c.ib > c.ia)
+    ok = hipMemcpyAsync(d_in.as<uint8_t>() + c.ia, h_in.as<uint8_t>() + c.ia, c.ib - c.ia, hipMemcpyHostToDevice,
+                        st) == hipSuccess;
+  const uint32_t ja = p.blk_base[c.a], jn = p.blk_base[c.b] - p.blk_base[c.a];
+  if (ok && c.direct && jn) {
+    ok = hipMemcpyAsync(dg.src + ja, hg.src + ja, 8ull * jn, hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemcpyAsync(dg.dst + ja, hg.dst + ja, 8ull * jn, hipMemcpyHostToDevice, st) == hipSuccess &&
+         hipMemcpyAsync(dg.len + ja, hg.len + ja, 4ull * jn, hipMemcpyHostToDevice, st) == hipSuccess &&
+         fsg_gather_blocks(dg.src + ja, dg.len + ja, dg.dst + ja, jn, d_in.as<uint8_t>(), st) == FSG_SUCCESS;
+  }
+  // this chunk's offsets, lengths and caps: four column slices, or (one
+  // chunk: the whole batch) the four columns in one copy -- per-copy
+  // latency dominates a small batch
+  const uint32_t a = c.a, cn = c.cn;
+  if (p.n_chunks() == 1) {
+    ok = ok && hipMemcpyAsync(d.in_off, h.in_off, MetaColumns::kUpBytesPerBody * (size_t)bt.n,
+                              hipMemcpyHostToDevice, st) == hipSuccess;
+  } else {
+    ok = ok && hipMemcpyAsync(d.in_off + a, h.in_off + a, 8ull * cn, hipMemcpyHostToDevice, st) == hipSuccess;
+    ok = ok && hipMemcpyAsync(d.out_off + a, h.out_off + a, 8ull * cn, hipMemcpyHostToDevice, st) == hipSuccess;
+    ok = ok && hipMemcpyAsync(d.in_len + a, h.in_len + a, 4ull * cn, hipMemcpyHostToDevice, st) == hipSuccess;
+    ok = ok && hipMemcpyAsync(d.out_cap + a, h.out_cap + a, 4ull * cn, hipMemcpyHostToDevice, st) == hipSuccess;
+  }
+  if (!ok) fprintf(stderr, "[flare-snappy-gpu] H2D copy failed on device %d\n", id);
+  return ok;
+}
+
+// The batch call (compress, then the pack pass of a packed chunk; or decode /
+// validate) and the workspace's report header behind it.
+bool Device::launch_chunk(Batch& bt, const Chunk& c) {
+  const MetaColumns& d = bt.d;
+  const bool validate = bt.validate();
+  const uint32_t a = c.a, cn = c.cn;
+  const int slot = c.slot;
+  hipStream_t st = streams[slot];
+  int rc;
+  if (bt.compress()) {
+    uint32_t cmax = 0;
+    for (uint32_t i = a; i < c.b; ++i) cmax = std::max(cmax, bt.plan.in_len[i]);
+    const size_t ws = fsg_compress_workspace_bytes(cn, cmax);
+    void* wsp = d_ws[slot].reserve(ws) ? d_ws[slot].p : nullptr;  // no workspace -> LDS-table kernel
+    rc = fsg_compress_batch(d_in.as<uint8_t>(), d.in_off + a, d.in_len + a, cn, cmax, d_out.as<uint8_t>(),
+                            d.out_off + a, d.out_len + a, d.status + a, wsp, wsp ? ws : 0, st);
+    bt.call[slot] = CallArgs{cn, cmax, wsp ? ws : 0};
+    if (rc == FSG_SUCCESS && bt.plan.packed[c.k]) {
+      // dense copies of the outputs, 16-byte aligned (an adopted output that
+      // later feeds a decode keeps fsg_gather_blocks' 16-byte path)
+      const size_t pws = fsg_pack_workspace_bytes(cn);
+      if (d_pack[slot].reserve(c.ob - c.oa) && d_pmeta[slot].reserve(8 + 8ull * cn + pws)) {
+        auto* d_total = d_pmeta[slot].as<uint64_t>();
+        rc = fsg_pack_batch(d_out.as<uint8_t>(), d.out_off + a, d.out_len + a, d.status + a, cn, 16,
+                            d_pack[slot].as<uint8_t>(), d_total + 1, d_total, d_total + 1 + cn, pws, st);
+      } else {
+        rc = FSG_ERR_HIP;
+      }
+    }
+  } else {
+    // two-pass decoder workspace (tag bitmap); without it the single-pass kernel runs
+    const size_t ws = validate ? 0 : fsg_decompress_workspace_bytes(cn, c.ib - c.ia);
+    void* wsp = ws && d_ws[slot].reserve(ws) ? d_ws[slot].p : nullptr;
+    rc = fsg_decompress_batch(d_in.as<uint8_t>(), d.in_off + a, d.in_len + a, cn,
+                              validate ? nullptr : d_out.as<uint8_t>(), validate ? nullptr : d.out_off + a,
+                              validate ? nullptr : d.out_cap + a, d.out_len + a, d.status + a,
+                              validate ? FSG_FLAG_VALIDATE_ONLY : 0u, wsp, wsp ? ws : 0, st);
+    bt.call[slot] = CallArgs{cn, 0, wsp ? ws : 0};
+  }
+  // the workspace's counter header, behind the batch's passes on its stream
+  // (a failed reserve() left no workspace: the routing rule alone reports it)
+  const size_t rep_bytes = fsg_report_header_bytes();
+  if (rc == FSG_SUCCESS && bt.call[slot].ws_bytes >= rep_bytes &&
+      hipMemcpyAsync(h_rep.as<uint8_t>() + rep_bytes * slot, d_ws[slot].p, rep_bytes, hipMemcpyDeviceToHost, st) !=
+          hipSuccess)
+    rc = FSG_ERR_HIP;
+  if (rc != FSG_SUCCESS)
+    fprintf(stderr, "[flare-snappy-gpu] batch launch failed on device %d: %s\n", id, fsg_last_error());
+  return rc == FSG_SUCCESS;
+}
+
+// D2H: the lengths and statuses (one chunk: both columns in one copy), then
+// the chunk's output slots, or a packed chunk's total.
+bool Device::download_chunk(Batch& bt, const Chunk& c) {
+  const BatchPlan& p = bt.plan;
+  const MetaColumns &h = bt.h, &d = bt.d;
+  const uint32_t a = c.a, cn = c.cn;
+  const bool packed = p.packed[c.k];
+  hipStream_t st = streams[c.slot];
+  const bool ok =
+      (p.n_chunks() == 1
+           ? hipMemcpyAsync(h.out_len, d.out_len, MetaColumns::kDownBytesPerBody * (size_t)bt.n,
+                            hipMemcpyDeviceToHost, st) == hipSuccess
+           : hipMemcpyAsync(h.out_len + a, d.out_len + a, 4ull * cn, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                 hipMemcpyAsync(h.status + a, d.status + a, 4ull * cn, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+      (bt.validate() || c.ob == c.oa ||
+       (packed ? hipMemcpyAsync(h_total.as<uint64_t>() + c.slot, d_pmeta[c.slot].p, sizeof(uint64_t),
+                                hipMemcpyDeviceToHost, st)
+               : hipMemcpyAsync(bt.hout + p.hbase[c.k], d_out.as<uint8_t>() + c.oa, c.ob - c.oa,
+                                hipMemcpyDeviceToHost, st)) == hipSuccess);
+  if (ok && !bt.validate() && !packed) bt.d2h += c.ob - c.oa;
+  if (!ok) fprintf(stderr, "[flare-snappy-gpu] D2H copy failed on device %d\n", id);
+  return ok;
+}
+
+// Path report of the slot's finished batch call.
+void Device::read_report(Batch& bt, int slot) {
+  const CallArgs& call = bt.call[slot];
+  const void* hdr = call.ws_bytes ? h_rep.as<uint8_t>() + fsg_report_header_bytes() * slot : nullptr;
+  uint64_t fb = 0, sp = 0;
+  if (bt.compress()) {
+    fsg_encode_report r;
+    if (fsg_compress_report(hdr, call.n, call.max_len, call.ws_bytes, &r) != FSG_SUCCESS) return;
+    fb = r.fallback_messages;
+    sp = r.no_workspace_messages;
+  } else {
+    fsg_decode_report r;
+    if (fsg_decompress_report(hdr, call.n, call.ws_bytes, bt.validate() ? FSG_FLAG_VALIDATE_ONLY : 0u, &r) !=
+        FSG_SUCCESS)
+      return;
+    fb = r.fallback_messages;
+    // validate-only is single-pass by design
+    sp = r.path == FSG_PATH_NO_WORKSPACE || r.path == FSG_PATH_FORCED ? r.single_pass_messages : 0;
+  }
+  bt.fb_messages += fb;
+  bt.fb_batches += fb ? 1 : 0;
+  bt.single_pass += sp;
+}
+
+// Waits for the slot's chunk (if one is in flight), downloads a packed
+// chunk's outputs, and scatters the results to the callers' cord_bufs.
+void Device::finish_chunk(Batch& bt, int slot) {
+  const int k = bt.pending[slot];
+  if (k < 0) return;
+  bt.pending[slot] = -1;
+  if (hipStreamSynchronize(streams[slot]) != hipSuccess) {
+    fprintf(stderr, "[flare-snappy-gpu] stream error on device %d\n", id);
+    bt.failed = true;
+    return;
+  }
+  read_report(bt, slot);
+  const BatchPlan& p = bt.plan;
+  const uint32_t* out_len = bt.h.out_len;
+  const int32_t* status = bt.h.status;
+  // where message i's bytes are on the host, the slab they are adopted from
+  const uint32_t ka = p.cut[k], kb = p.cut[k + 1];
+  const bool packed = p.packed[k];
+  uint8_t* obase = bt.hout + p.hbase[k];
+  OutSlab* oslab = bt.slab;
+  bool oadopt = bt.adopt;
+  if (packed) {
+    // the lengths and statuses are here: lay the packed outputs out as the
+    // device did, take a slab for exactly that many bytes, download them
+    bt.poff.resize(kb - ka);
+    const uint64_t tot = packed_layout(status, out_len, ka, kb, bt.poff.data());
+    if (tot != h_total.as<uint64_t>()[slot]) {
+      fprintf(stderr, "[flare-snappy-gpu] packed size mismatch on device %d\n", id);
+      bt.failed = true;
       return;
     }
-    read_report(slot);
-    // where message i's bytes are on the host, the slab they are adopted from
-    const uint32_t ka = cut[k];
-    uint8_t* obase = hout + hbase[k];
-    OutSlab* oslab = slab;
-    bool oadopt = adopt;
-    if (packed[k]) {
-      // the lengths and statuses are here: lay the packed outputs out as the
-      // device did, take a slab for exactly that many bytes, download them
-      const uint32_t kb = cut[k + 1];
-      poff.resize(kb - ka);
-      uint64_t tot = 0;
-      for (uint32_t i = ka; i < kb; ++i) {
-        poff[i - ka] = tot;
-        tot += align16(status[i] != FSG_OK ? 0 : out_len[i]);
-      }
-      if (tot != h_total.as<uint64_t>()[slot]) {
-        fprintf(stderr, "[flare-snappy-gpu] packed size mismatch on device %d\n", id);
-        failed = true;
-        return;
-      }
-      oslab = AcquireOutSlab(tot + 16);
-      oadopt = oslab && !OutSlabsUnderPressure();
-      obase = oslab ? OutSlabData(oslab) : (h_pack.reserve(tot + 16) ? h_pack.as<uint8_t>() : nullptr);
-      if (obase == nullptr ||
-          (tot && (hipMemcpyAsync(obase, d_pack[slot].p, tot, hipMemcpyDeviceToHost, streams[slot]) != hipSuccess ||
-                   hipStreamSynchronize(streams[slot]) != hipSuccess))) {
-        fprintf(stderr, "[flare-snappy-gpu] packed D2H failed on device %d\n", id);
-        if (oslab) OutSlabRelease(oslab);
-        failed = true;
-        return;
-      }
-      d2h += tot;
-      ++packed_chunks;
+    oslab = AcquireOutSlab(tot + 16);
+    oadopt = oslab && !OutSlabsUnderPressure();
+    obase = oslab ? OutSlabData(oslab) : (h_pack.reserve(tot + 16) ? h_pack.as<uint8_t>() : nullptr);
+    if (obase == nullptr ||
+        (tot && (hipMemcpyAsync(obase, d_pack[slot].p, tot, hipMemcpyDeviceToHost, streams[slot]) != hipSuccess ||
+                 hipStreamSynchronize(streams[slot]) != hipSuccess))) {
+      fprintf(stderr, "[flare-snappy-gpu] packed D2H failed on device %d\n", id);
+      if (oslab) OutSlabRelease(oslab);
+      bt.failed = true;
+      return;
     }
-    // ---- scatter: append results to the callers' cord_bufs (serial: page
-    // faults from many threads at once measured 3x slower than one thread)
-    for (uint32_t i = cut[k]; i < cut[k + 1]; ++i) {
-      Request* r = reqs[i];
-      if (skip[i] == 2) continue;  // for the host codec
-      r->handled = true;
-      if (skip[i] || status[i] != FSG_OK) {
-        r->ok = false;
-        ++corrupt;
-        continue;
-      }
-      r->ok = true;
-      bytes_in += in_len[i];
-      if (validate) continue;
-      const uint32_t L = out_len[i];
-      uint8_t* bytes = obase + (packed[k] ? poff[i - ka] : out_off[i] - out_off[ka]);
-      if (oadopt && L >= kAdoptMin) {
-        OutSlabRef(oslab);
-        r->out->append_user_data(bytes, L, AdoptedDeleter);
-        ++adopted;
-      } else {
-        r->out->append(bytes, L);
-      }
-      bytes_out += L;
-    }
-    if (packed[k] && oslab) OutSlabRelease(oslab);  // the adopted ranges keep it alive
-  };
-  for (size_t k = 0; k < n_chunks && !failed; ++k) {
-    const int slot = (int)(k % kSlots);
-    finish(slot);  // its previous chunk (staging regions are disjoint, streams are not)
-    if (failed) break;
-    const uint32_t a = cut[k], b = cut[k + 1], cn = b - a;
-    // ---- gather: cord_buf backing blocks (cord_buf.cc:1469-1475) -- pinned
-    // ones become descriptors for the device gather, the rest is staged
-    const size_t ia = in_off[a], ib = b < n ? in_off[b] : pos_in;
-    std::atomic<uint64_t> staged{0}, direct{0};
-    parallel_for(a, b, ib - ia, [&](uint32_t i) {
-      if (skip[i]) return;
-      const cord_buf& in = *reqs[i]->in;
-      size_t w = 0;
-      uint64_t st = 0, dr = 0;
-      for (size_t blk = 0; blk < in.backing_block_num(); ++blk) {
-        std::string_view v = in.backing_block(blk);
-        const uint32_t j = blk_base[i] + (uint32_t)blk;
-        g_dst[j] = in_off[i] + w;
-        if (v.size() >= 1024 && IsPinned(v.data(), v.size())) {
-          g_src[j] = reinterpret_cast<uint64_t>(v.data());
-          g_len[j] = (uint32_t)v.size();
-          dr += v.size();
-        } else {
-          g_src[j] = 0;
-          g_len[j] = 0;
-          memcpy(hin + in_off[i] + w, v.data(), v.size());
-          st += v.size();
-        }
-        w += v.size();
-      }
-      staged += st;
-      direct += dr;
-    });
-    hipStream_t st = streams[slot];
-    const size_t oa = out_off[a], ob = b < n ? out_off[b] : pos_out;
-    bool ok = true;
-    if (staged.load() && ib > ia)
-      ok = hipMemcpyAsync(d_in.as<uint8_t>() + ia, hin + ia, ib - ia, hipMemcpyHostToDevice, st) == hipSuccess;
-    const uint32_t ja = blk_base[a], jn = blk_base[b] - blk_base[a];
-    if (ok && direct.load() && jn) {
-      ok = hipMemcpyAsync(dg_src + ja, g_src + ja, 8ull * jn, hipMemcpyHostToDevice, st) == hipSuccess &&
-           hipMemcpyAsync(dg_dst + ja, g_dst + ja, 8ull * jn, hipMemcpyHostToDevice, st) == hipSuccess &&
-           hipMemcpyAsync(dg_len + ja, g_len + ja, 4ull * jn, hipMemcpyHostToDevice, st) == hipSuccess &&
-           fsg_gather_blocks(dg_src + ja, dg_len + ja, dg_dst + ja, jn, d_in.as<uint8_t>(), st) == FSG_SUCCESS;
-    }
-    // this chunk's offsets, lengths and caps: four column slices, or (one
-    // chunk: the whole batch) the four columns in one copy -- per-copy
-    // latency dominates a small batch
-    if (n_chunks == 1) {
-      ok = ok && hipMemcpyAsync(d_in_off, in_off, 24ull * n, hipMemcpyHostToDevice, st) == hipSuccess;
-    } else {
-      ok = ok && hipMemcpyAsync(d_in_off + a, in_off + a, 8ull * cn, hipMemcpyHostToDevice, st) == hipSuccess;
-      ok = ok && hipMemcpyAsync(d_out_off + a, out_off + a, 8ull * cn, hipMemcpyHostToDevice, st) == hipSuccess;
-      ok = ok && hipMemcpyAsync(d_in_len + a, in_len + a, 4ull * cn, hipMemcpyHostToDevice, st) == hipSuccess;
-      ok = ok && hipMemcpyAsync(d_out_cap + a, out_cap + a, 4ull * cn, hipMemcpyHostToDevice, st) == hipSuccess;
-    }
-    if (!ok) {
-      fprintf(stderr, "[flare-snappy-gpu] H2D copy failed on device %d\n", id);
-      failed = true;
-      break;
-    }
-    int rc;
-    if (compress) {
-      uint32_t cmax = 0;
-      for (uint32_t i = a; i < b; ++i) cmax = std::max(cmax, in_len[i]);
-      const size_t ws = fsg_compress_workspace_bytes(cn, cmax);
-      void* wsp = d_ws[slot].reserve(ws) ? d_ws[slot].p : nullptr;  // no workspace -> LDS-table kernel
-      rc = fsg_compress_batch(d_in.as<uint8_t>(), d_in_off + a, d_in_len + a, cn, cmax,
-                              d_out.as<uint8_t>(), d_out_off + a, d_out_len + a, d_status + a, wsp,
-                              wsp ? ws : 0, st);
-      call[slot] = CallArgs{cn, cmax, wsp ? ws : 0};
-      if (rc == FSG_SUCCESS && packed[k]) {
-        // dense copies of the outputs, 16-byte aligned (an adopted output that
-        // later feeds a decode keeps fsg_gather_blocks' 16-byte path)
-        const size_t pws = fsg_pack_workspace_bytes(cn);
-        if (d_pack[slot].reserve(ob - oa) && d_pmeta[slot].reserve(8 + 8ull * cn + pws)) {
-          auto* d_total = d_pmeta[slot].as<uint64_t>();
-          rc = fsg_pack_batch(d_out.as<uint8_t>(), d_out_off + a, d_out_len + a, d_status + a, cn, 16,
-                              d_pack[slot].as<uint8_t>(), d_total + 1, d_total, d_total + 1 + cn, pws, st);
-        } else {
-          rc = FSG_ERR_HIP;
-        }
-      }
-    } else {
-      // two-pass decoder workspace (tag bitmap); without it the single-pass kernel runs
-      const size_t ws = validate ? 0 : fsg_decompress_workspace_bytes(cn, ib - ia);
-      void* wsp = ws && d_ws[slot].reserve(ws) ? d_ws[slot].p : nullptr;
-      rc = fsg_decompress_batch(d_in.as<uint8_t>(), d_in_off + a, d_in_len + a, cn,
-                                validate ? nullptr : d_out.as<uint8_t>(), validate ? nullptr : d_out_off + a,
-                                validate ? nullptr : d_out_cap + a, d_out_len + a, d_status + a,
-                                validate ? FSG_FLAG_VALIDATE_ONLY : 0u, wsp, wsp ? ws : 0, st);
-      call[slot] = CallArgs{cn, 0, wsp ? ws : 0};
-    }
-    // the workspace's counter header, behind the batch's passes on its stream
-    // (a failed reserve() left no workspace: the routing rule alone reports it)
-    if (rc == FSG_SUCCESS && call[slot].ws_bytes >= rep_bytes &&
-        hipMemcpyAsync(h_rep.as<uint8_t>() + rep_bytes * slot, d_ws[slot].p, rep_bytes, hipMemcpyDeviceToHost, st) !=
-            hipSuccess)
-      rc = FSG_ERR_HIP;
-    if (rc != FSG_SUCCESS) {
-      fprintf(stderr, "[flare-snappy-gpu] batch launch failed on device %d: %s\n", id, fsg_last_error());
-      failed = true;
-      break;
-    }
-    ok = (n_chunks == 1
-              ? hipMemcpyAsync(out_len, d_out_len, 8ull * n, hipMemcpyDeviceToHost, st) == hipSuccess
-              : hipMemcpyAsync(out_len + a, d_out_len + a, 4ull * cn, hipMemcpyDeviceToHost, st) == hipSuccess &&
-                    hipMemcpyAsync(status + a, d_status + a, 4ull * cn, hipMemcpyDeviceToHost, st) == hipSuccess) &&
-         (validate || ob == oa ||
-          (packed[k] ? hipMemcpyAsync(h_total.as<uint64_t>() + slot, d_pmeta[slot].p, sizeof(uint64_t),
-                                      hipMemcpyDeviceToHost, st)
-                     : hipMemcpyAsync(hout + hbase[k], d_out.as<uint8_t>() + oa, ob - oa, hipMemcpyDeviceToHost,
-                                      st)) == hipSuccess);
-    if (ok && !validate && !packed[k]) d2h += ob - oa;
-    if (!ok) {
-      fprintf(stderr, "[flare-snappy-gpu] D2H copy failed on device %d\n", id);
-      failed = true;
-      break;
-    }
-    pending[slot] = (int)k;
+    bt.d2h += tot;
+    ++bt.packed_chunks;
   }
-  for (int s2 = 0; s2 < kSlots; ++s2) {  // drain (a failed batch leaves later chunks unhandled)
-    if (failed) {
-      if (pending[s2] >= 0) (void)hipStreamSynchronize(streams[s2]);
-      pending[s2] = -1;
+  // ---- scatter: append results to the callers' cord_bufs (serial: page
+  // faults from many threads at once measured 3x slower than one thread)
+  for (uint32_t i = ka; i < kb; ++i) {
+    Request* r = bt.reqs[i];
+    if (p.skip[i] == 2) continue;  // for the host codec
+    r->handled = true;
+    if (p.skip[i] || status[i] != FSG_OK) {
+      r->ok = false;
+      ++bt.corrupt;
+      continue;
+    }
+    r->ok = true;
+    bt.bytes_in += p.in_len[i];
+    if (bt.validate()) continue;
+    const uint32_t L = out_len[i];
+    uint8_t* bytes = obase + (packed ? bt.poff[i - ka] : p.out_off[i] - p.out_off[ka]);
+    if (oadopt && L >= kAdoptMin) {
+      OutSlabRef(oslab);
+      r->out->append_user_data(bytes, L, AdoptedDeleter);
+      ++bt.adopted;
     } else {
-      finish(s2);
+      r->out->append(bytes, L);
+    }
+    bt.bytes_out += L;
+  }
+  if (packed && oslab) OutSlabRelease(oslab);  // the adopted ranges keep it alive
+}
+
+// Finishes the chunks still in flight; a failed batch only waits for their
+// streams and leaves them, like every later chunk, unhandled.
+void Device::drain(Batch& bt) {
+  for (int slot = 0; slot < kSlots; ++slot) {
+    if (bt.failed) {
+      if (bt.pending[slot] >= 0) (void)hipStreamSynchronize(streams[slot]);
+      bt.pending[slot] = -1;
+    } else {
+      finish_chunk(bt, slot);
     }
   }
-  if (slab) OutSlabRelease(slab);  // the adopted ranges keep it alive
+}
+
+void Device::add_counters(const Batch& bt, Counters* ctr) {
   ctr->batches += 1;
-  ctr->messages += n;
-  ctr->bytes_in += bytes_in;
-  ctr->bytes_out += bytes_out;
-  ctr->adopted += adopted;
-  ctr->failures += corrupt;
-  ctr->d2h_bytes += d2h;
-  ctr->packed_chunks += packed_chunks;
-  ctr->device_fallback_messages += fb_messages;
-  ctr->device_single_pass_messages += single_pass;
-  ctr->device_fallback_batches += fb_batches;
+  ctr->messages += bt.n;
+  ctr->bytes_in += bt.bytes_in;
+  ctr->bytes_out += bt.bytes_out;
+  ctr->adopted += bt.adopted;
+  ctr->failures += bt.corrupt;
+  ctr->d2h_bytes += bt.d2h;
+  ctr->packed_chunks += bt.packed_chunks;
+  ctr->device_fallback_messages += bt.fb_messages;
+  ctr->device_single_pass_messages += bt.single_pass;
+  ctr->device_fallback_batches += bt.fb_batches;
   uint64_t mb = ctr->max_batch.load();
-  while (n > mb && !ctr->max_batch.compare_exchange_weak(mb, n)) {
+  while (bt.n > mb && !ctr->max_batch.compare_exchange_weak(mb, bt.n)) {
   }
-  return !failed;
 }
 
 // Devices from FLARE_SNAPPY_GPU_DEVICES ("0x3" / "3" = a mask, "0,2" = a
@@ -813,16 +800,10 @@ struct SnappyGpuCodec::Impl {
         ctr.cpu_messages += 1;
       }
     } else {
-      // contiguous ranges balanced by input bytes (shard.byte_balanced_ranges)
-      size_t total = 0;
-      for (auto& r : rs) total += r.in->size() + 64;
-      std::vector<size_t> cuts{0};
-      size_t acc = 0;
-      for (size_t i = 0; i < rs.size() && cuts.size() < nd; ++i) {
-        acc += rs[i].in->size() + 64;
-        if (acc * nd >= total * cuts.size() && i + 1 < rs.size()) cuts.push_back(i + 1);
-      }
-      cuts.push_back(rs.size());
+      // contiguous ranges balanced by input bytes, a body counting 64 more than its size
+      std::vector<uint64_t> sizes(rs.size());
+      for (size_t i = 0; i < rs.size(); ++i) sizes[i] = rs[i].in->size() + 64;
+      const std::vector<size_t> cuts = byte_balanced_cuts(sizes.data(), sizes.size(), nd);
       auto part = [&](size_t p) {
         std::vector<Request*> batch;
         for (size_t i = cuts[p]; i < cuts[p + 1]; ++i) batch.push_back(&rs[i]);

@@ -12,12 +12,19 @@
 //   * otherwise a device batch: concurrent single-message calls are
 //     coalesced.  The first caller to find a device idle becomes that
 //     device's leader and runs every queued request as one batch
-//       gather (cord_buf blocks -> device; pinned blocks are read by the GPU
-//       itself, others staged through pinned memory) -> H2D ->
-//       fsg_{compress,decompress}_batch -> D2H into a pinned output slab ->
-//       scatter (outputs adopted zero-copy with append_user_data, small ones
-//       copied)
-//     and keeps leading while requests keep arriving; followers park on a
+//     (Device::run).  The batch's plan -- which bodies the device takes,
+//     their slots, the chunk cuts, which chunks pack, the D2H target -- is
+//     host arithmetic in batch_plan.h (plan_batch); run reserves the buffers
+//     for it and takes each chunk through the stages
+//       gather_chunk (cord_buf blocks: pinned ones become descriptors the GPU
+//       reads itself, others are staged through pinned memory) ->
+//       upload_chunk (H2D) -> launch_chunk (fsg_{compress,decompress}_batch,
+//       fsg_pack_batch for a packed chunk) -> download_chunk (D2H into a
+//       pinned output slab) -> finish_chunk (wait, path report, a packed
+//       chunk's download, scatter: outputs adopted zero-copy with
+//       append_user_data, small ones copied)
+//     on three streams, then drain and add_counters.  The leader
+//     keeps leading while requests keep arriving; followers park on a
 //     latch (park hooks: a flare::fiber_latch, flare/fiber/fiber_latch.h:
 //     10-28, when the host framework installs one; a condition variable by
 //     default).  Devices come from a mask (InitDevices / FLARE_SNAPPY_GPU_DEVICES).

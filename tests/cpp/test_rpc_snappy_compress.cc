@@ -18,6 +18,9 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/flare_snappy_gpu.h"
+#include "../../include/flare_snappy_host.h"
+#include "batch_plan.h"
 #include "compress.h"
 #include "cord_buf.h"
 #include "gpu_codec.h"
@@ -197,6 +200,18 @@ TEST_CPU(snappy_message_wire_format) {
   ASSERT_TRUE(p.ParseFromString(w));
   ASSERT_EQ(p.numbers_size(), 4);
   ASSERT_EQ(p.numbers(3), -1);
+}
+
+// batch_plan.h restates the slot bound (it cannot call the GPU library)
+TEST_CPU(batch_plan_slot_bound_is_the_librarys) {
+  // the largest n whose bound fits u32: 32 + n + n / 6 = 0xfffffffe, and 2^32 one above
+  const size_t n_max = 3681400511ull;
+  ASSERT_EQ(flare::gpu::max_compressed_length(n_max), (size_t)0xfffffffeull);
+  ASSERT_EQ(flare::gpu::max_compressed_length(n_max + 1), (size_t)1 << 32);
+  for (size_t n : {(size_t)0, (size_t)1, (size_t)5, (size_t)6, (size_t)65536, (size_t)(0xffffffffull / 2), n_max}) {
+    ASSERT_EQ(flare::gpu::max_compressed_length(n), fsg_max_compressed_length(n));
+    ASSERT_EQ(flare::gpu::max_compressed_length(n), fsh_max_compressed_length(n));
+  }
 }
 
 // ------------------------------------------------------------------ GPU tests
