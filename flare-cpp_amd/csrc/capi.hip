@@ -53,6 +53,8 @@ constexpr OptDesc kOptDesc[fsg::kOptCount] = {
     {"lz4_encode_wave_per_cu", "FSG_L4_ENC_WAVE_PER_CU", 0},
     {"lz4f_force_serial", "FSG_L4F_FORCE_SERIAL", 0},
     {"lz4f_block_wave_min", "FSG_L4F_BLOCK_WAVE_MIN", -1},
+    {"lz4f_nosize_fast", "FSG_L4F_NOSIZE_FAST", 0},
+    {"lz4f_length_wave_min", "FSG_L4F_LENGTH_WAVE_MIN", -1},
 };
 // DecodeOpts' initialisers (decode_v4_plan.h, which the CPU test of the launch
 // plan uses as "the defaults") are this table's
@@ -621,12 +623,30 @@ int fsg_lz4f_decompress_batch(const uint8_t* d_in, const uint64_t* d_in_off, con
                               void* d_workspace, size_t workspace_bytes, void* stream) {
   if (n_msgs == 0) return FSG_SUCCESS;
   if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status ||
-      !d_workspace || fsg::lz4f_decompress_block_capacity(n_msgs, workspace_bytes) == 0)
+      !d_workspace)
     return FSG_ERR_INVALID_ARG;
+  const fsg::u32 entries = fsg::lz4f_decompress_block_capacity(n_msgs, workspace_bytes);
+  if (entries == 0) return FSG_ERR_INVALID_ARG;
   return record(fsg::launch_lz4f_decode(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
                                         d_status, d_workspace, workspace_bytes,
-                                        fsg::opt(fsg::kOptLz4fForceSerial) != 0, (hipStream_t)stream),
+                                        fsg::opt(fsg::kOptLz4fForceSerial) != 0,
+                                        fsg::opt(fsg::kOptLz4fNosizeFast) != 0,
+                                        fsg::lz4f_length_wave_min(fsg::opt(fsg::kOptLz4fLengthWaveMin)),
+                                        (hipStream_t)stream),
                 "fsg_lz4f_decompress_batch");
+}
+
+int fsg_lz4f_decoded_lengths_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                   uint32_t n_msgs, uint64_t* d_length, int32_t* d_status, void* d_workspace,
+                                   size_t workspace_bytes, void* stream) {
+  if (n_msgs == 0) return FSG_SUCCESS;
+  if (!d_in || !d_in_off || !d_in_len || !d_length || !d_status || !d_workspace) return FSG_ERR_INVALID_ARG;
+  const fsg::u32 entries = fsg::lz4f_decompress_block_capacity(n_msgs, workspace_bytes);
+  if (entries == 0) return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_lz4f_decoded_lengths(
+                    d_in, d_in_off, d_in_len, n_msgs, d_length, d_status, d_workspace, workspace_bytes,
+                    fsg::lz4f_length_wave_min(fsg::opt(fsg::kOptLz4fLengthWaveMin)), (hipStream_t)stream),
+                "fsg_lz4f_decoded_lengths_batch");
 }
 
 int fsg_lz4f_content_sizes_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
@@ -672,6 +692,8 @@ int fsg_lz4f_decompress_report(const void* header_host_copy, uint32_t n_msgs, si
   out->serial_forced = c.serial_forced;
   out->checksummed_units = c.checksummed_units;
   out->inner_fallback_blocks = c.inner_fallback;
+  out->fast_nosize_messages = c.fast_nosize_messages;
+  out->fast_nosize_blocks = c.fast_nosize_blocks;
   return FSG_SUCCESS;
 }
 

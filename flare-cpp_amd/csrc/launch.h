@@ -91,7 +91,14 @@ hipError_t launch_lz4f_encode(const u8* in, const u64* in_off, const u32* in_len
                               size_t ws_bytes, u64 wave_min, hipStream_t stream);
 hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
-                              size_t ws_bytes, bool force_serial, hipStream_t stream);
+                              size_t ws_bytes, bool force_serial, bool nosize_fast, u32 length_wave_min,
+                              hipStream_t stream);
+// the length pass's wave threshold from option lz4f_length_wave_min (-1: the automatic rule)
+u32 lz4f_length_wave_min(i64 option);
+// fsg_lz4f_decoded_lengths_batch: on a decompress workspace
+hipError_t launch_lz4f_decoded_lengths(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* lengths,
+                                       i32* status, void* ws, size_t ws_bytes, u32 length_wave_min,
+                                       hipStream_t stream);
 hipError_t launch_lz4f_content_sizes(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* sizes,
                                      i32* status, hipStream_t stream);
 
@@ -117,6 +124,7 @@ struct Lz4fDecodeHeaderCounts {
   u32 fast_messages, fast_blocks, empty_messages;
   u32 serial_linked, serial_no_size, serial_rejected, serial_forced;
   u32 checksummed_units, inner_fallback;
+  u32 fast_nosize_messages, fast_nosize_blocks;
 };
 void lz4f_encode_header_counts(const void* header, Lz4fEncodeHeaderCounts* c);
 void lz4f_decode_header_counts(const void* header, Lz4fDecodeHeaderCounts* c);

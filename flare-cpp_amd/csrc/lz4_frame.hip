@@ -21,8 +21,16 @@
 // checksum, status, length) -> finish (a lane per message: content checksum,
 // status; and the serial decoder, lz4_frame_format.h, for linked blocks,
 // frames without a content size and every frame the fast route did not accept).
+// With option lz4f_nosize_fast, frames with independent blocks and no content
+// size go block-parallel too: index lists their blocks with the length unknown,
+// length (a lane per small block, a wave per large one: lz4_frame_length.h)
+// finds every block's decoded length, place (a wave per message: prefix sum of
+// the lengths) gives the blocks their places in the slot; stage, the block
+// decoder, verdict and finish go on as for the sized frames.
+// fsg_lz4f_decoded_lengths_batch is index, length and the sum alone.
 #include "launch.h"
 #include "lz4_frame_format.h"
+#include "lz4_frame_length.h"
 #include "snappy_device.h"
 
 namespace fsg {
@@ -42,13 +50,19 @@ constexpr u32 kFdFastMsgs = 1, kFdFastBlocks = 2, kFdEmpty = 3;
 constexpr u32 kFdLinked = 4, kFdNoSize = 5, kFdRejected = 6, kFdForced = 7;
 constexpr u32 kFdSums = 8, kFdInner = 9;
 constexpr u32 kFdStage = 10;    // u64
+constexpr u32 kFdNsMsgs = 12, kFdNsBlocks = 13;  // answered by the fast route without a content size
+constexpr u32 kFdBig = 14;      // length pass: blocks listed for the wave walk
+constexpr u32 kFdBigNext = 15;  // and the next of them to take
 constexpr u64 kHead = 256;
 
 // msg_route values
 constexpr u32 kRouteDone = 0, kRouteFast = 1, kRouteLinked = 2, kRouteNoSize = 3, kRouteRejected = 4,
               kRouteForced = 5;
+constexpr u32 kRouteNoSizeFast = 6;  // fast route without a content size (pending until finish accepts it)
 // block flags
 constexpr u32 kBlkRaw = 1, kBlkSum = 2, kBlkFailed = 4, kBlkListed = 8;
+constexpr u32 kBlkUnknown = 16;  // decoded length unknown: the length pass finds it
+constexpr u32 kBlkMaxShift = 8;  // with kBlkUnknown: log2 of the frame's block maximum, from this bit up
 
 constexpr u32 kNoFit = 0xFFFFFFFFu;
 
@@ -61,15 +75,7 @@ __host__ __device__ inline u64 enc_slot(u64 L) { return round_up(5 + L + L / 255
 // and of a stored block of sz bytes in the decompressor: varint32 + bytes
 __host__ __device__ inline u64 dec_slot(u64 sz) { return round_up(5 + sz, 16) + 16; }
 
-__device__ __forceinline__ u32 wave_scan(u32 v) {
-  const u32 lane = __lane_id();
-#pragma unroll
-  for (u32 d = 1; d < 64; d <<= 1) {
-    const u32 t = __shfl_up(v, d, 64);
-    v += lane >= d ? t : 0u;
-  }
-  return v;
-}
+__device__ __forceinline__ u32 wave_scan(u32 v) { return wave_incl_scan(v); }
 
 // adds `pred` lanes to a counter: one atomic for the wave's active lanes
 __device__ __forceinline__ void count_lanes(u32* ctr, bool pred) {
@@ -237,6 +243,70 @@ __global__ __launch_bounds__(64) void lz4f_sizes_kernel(const u8* __restrict__ i
   status[m] = st;
 }
 
+// The block structure of a frame without a content size, from the size words
+// alone: every size at most the block maximum (and not 0, unless zero_raw
+// allows an empty raw block, which the serial decoder accepts) and inside the
+// input with its block checksum, the end mark, the content checksum when
+// flagged, nothing after the frame.  *nb blocks, *need staging bytes for the
+// compressed ones, *xxh the stated content checksum.
+__device__ inline bool walk_blocks(const u8* ib, u64 n, const lz4f::Header& h, bool zero_raw, u32* nb, u64* need,
+                                   u32* xxh) {
+  const u32 bsum = (h.flg & lz4f::kFlgBlockSum) ? 4 : 0;
+  u64 ip = h.len, nd = 0;
+  u32 k = 0;
+  for (;; ++k) {
+    if (n - ip < 4) return false;
+    const u32 word = lz4f::rd32(ib + ip);
+    ip += 4;
+    if (word == 0) break;
+    const u32 sz = word & ~lz4f::kRawBit;
+    if ((sz == 0 && !zero_raw) || sz > h.block_max || n - ip < (u64)sz + bsum) return false;
+    if (!(word & lz4f::kRawBit)) {
+      if (sz == 0) return false;  // a compressed block has a token
+      nd += dec_slot(sz);
+    }
+    ip += sz + bsum;
+  }
+  *xxh = 0;
+  if (h.flg & lz4f::kFlgSum) {
+    if (n - ip < 4) return false;
+    *xxh = lz4f::rd32(ib + ip);
+    ip += 4;
+  }
+  if (ip != n) return false;
+  *nb = k;
+  *need = nd;
+  return true;
+}
+
+// The entries [base, base + nb) of a frame walk_blocks accepted: where the
+// stored bytes are, the flags with "length unknown", a staging slot from `at`
+// on for a compressed block (at = 0: none, the lengths call).  in_len,
+// out_off and out_cap stay 0 -- an empty body for the block decoder -- until
+// the place kernel knows the lengths.
+__device__ inline void list_unknown(const u8* ib, const lz4f::Header& h, u64 io, u32 nb, u32 base, u64 at,
+                                    BlockCols c) {
+  const u32 bsum = (h.flg & lz4f::kFlgBlockSum) ? 4 : 0;
+  const u32 common = kBlkListed | kBlkUnknown | (bsum ? kBlkSum : 0) |
+                     ((u32)(31 - __builtin_clz(h.block_max)) << kBlkMaxShift);
+  u64 ip = h.len;
+  for (u32 k = 0; k < nb; ++k) {
+    const u32 e = base + k;
+    const u32 word = lz4f::rd32(ib + ip);
+    const u32 sz = word & ~lz4f::kRawBit;
+    const bool raw = word & lz4f::kRawBit;
+    ip += 4;
+    c.src_off[e] = io + ip;
+    c.src_len[e] = sz;
+    c.flags[e] = common | (raw ? kBlkRaw : 0);
+    if (!raw && at) {
+      c.in_off[e] = at;
+      at += dec_slot(sz);
+    }
+    ip += sz + bsum;
+  }
+}
+
 // One lane per message: descriptor, route, and for the fast route the walk
 // over the block size words (two walks: sizes, then columns).
 __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ in, const u64* __restrict__ in_off,
@@ -244,7 +314,7 @@ __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ i
                                                       const u64* __restrict__ out_off, const u32* __restrict__ out_cap,
                                                       u32* __restrict__ out_len, i32* __restrict__ status, u32* hdr,
                                                       MsgCols mc, BlockCols c, u32 nb_cap, u64 stage_off,
-                                                      u64 stage_cap, u32 force_serial) {
+                                                      u64 stage_cap, u32 force_serial, u32 nosize_fast) {
   const u32 m = blockIdx.x * 64 + threadIdx.x;
   if (m >= n_msgs) return;
   const u8* ib = in + in_off[m];
@@ -280,7 +350,23 @@ __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ i
     return;
   }
   if (h.size == lz4f::kNoSize) {
-    mc.route[m] = kRouteNoSize;
+    if (!nosize_fast) {
+      mc.route[m] = kRouteNoSize;
+      return;
+    }
+    // no content size: the blocks' lengths are unknown until the length pass
+    mc.route[m] = kRouteRejected;
+    u32 nb, xxh;
+    u64 need;
+    if (!walk_blocks(ib, n, h, false, &nb, &need, &xxh)) return;
+    const u32 base = atomicAdd(&hdr[kFdBlocks], nb);
+    const u64 sb = atomicAdd(reinterpret_cast<unsigned long long*>(hdr + kFdStage), (unsigned long long)need);
+    if ((u64)base + nb > nb_cap || sb + need > stage_cap) return;
+    list_unknown(ib, h, in_off[m], nb, base, stage_off + sb, c);
+    mc.xxh[m] = xxh;
+    mc.first[m] = base;
+    mc.nb[m] = nb;
+    mc.route[m] = kRouteNoSizeFast;
     return;
   }
   // fast route: every block but the last is full
@@ -338,6 +424,165 @@ __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ i
   mc.first[m] = base;
   mc.nb[m] = nb;
   mc.route[m] = kRouteFast;
+}
+
+// ---- the length pass (frames without a content size)
+// One lane per claimed entry whose length is unknown: a raw block decodes to
+// its stored size, a compressed block of at most wave_min bytes to what
+// block_length says; a larger one is listed for lz4f_length_wave_kernel.  The
+// length goes to out_len and the list to status: both columns are idle until
+// the block decoder runs.
+__global__ __launch_bounds__(64) void lz4f_length_lane_kernel(const u8* __restrict__ in, u32* hdr, BlockCols c,
+                                                            u32 nb_cap, u32 wave_min) {
+  const u32 claimed = hdr[kFdBlocks] < nb_cap ? hdr[kFdBlocks] : nb_cap;
+  u32* const big = reinterpret_cast<u32*>(c.status);
+  for (u32 e = blockIdx.x * 64 + threadIdx.x; e < claimed; e += gridDim.x * 64) {
+    const u32 f = c.flags[e];
+    if (!(f & kBlkUnknown)) continue;
+    const u32 sz = c.src_len[e];
+    if (f & kBlkRaw) {
+      c.out_len[e] = sz;
+    } else if (sz > wave_min) {
+      big[atomicAdd(&hdr[kFdBig], 1u)] = e;  // each entry at most once: fewer than nb_cap
+    } else {
+      u64 len = 0;
+      if (lz4f::block_length(in + c.src_off[e], sz, 1ull << (f >> kBlkMaxShift), &len)) c.out_len[e] = (u32)len;
+      else c.flags[e] = f | kBlkFailed;
+    }
+  }
+}
+
+// One wave per listed block, taken from a counter: whichever wave is free
+// takes the next, so a frame's adjacent large blocks spread over the chip.
+__global__ __launch_bounds__(kLenWaves * 64) void lz4f_length_wave_kernel(const u8* __restrict__ in, u32* hdr,
+                                                                        BlockCols c) {
+  __shared__ u32 ring_s[kLenWaves][kLenRing / 4];
+  const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const u32 lane = threadIdx.x & 63;
+  const u32 count = hdr[kFdBig];
+  const u32* const big = reinterpret_cast<const u32*>(c.status);
+  for (;;) {  // lane 0 adds 1; its result is the index
+    const u32 got = atomicAdd(&hdr[kFdBigNext], lane == 0 ? 1u : 0u);
+    const u32 idx = (u32)__builtin_amdgcn_readfirstlane((int)got);
+    if (idx >= count) break;
+    const u32 e = (u32)__builtin_amdgcn_readfirstlane((int)big[idx]);
+    const u32 f = (u32)__builtin_amdgcn_readfirstlane((int)c.flags[e]);
+    const u32 sz = (u32)__builtin_amdgcn_readfirstlane((int)c.src_len[e]);
+    u32 len = 0;
+    const bool ok = lz4f_wave_block_length(in + c.src_off[e], sz, 1u << (f >> kBlkMaxShift), ring_s[wv], lane, &len);
+    if (lane == 0) {
+      if (ok) c.out_len[e] = len;
+      else c.flags[e] = f | kBlkFailed;
+    }
+  }
+}
+
+// One wave per message on the pending route: the blocks' places from an
+// exclusive sum over their lengths, 64 at a time.  A frame with a block that
+// has no length, or longer than its slot, leaves the route: its entries are
+// unlisted, so that stage and the block decoder write nothing for it, and the
+// serial decoder gives its verdict.  lengths != nullptr
+// (fsg_lz4f_decoded_lengths_batch): the sum and its status are the answer.
+__global__ __launch_bounds__(256) void lz4f_place_kernel(u32 n_msgs, const u64* __restrict__ out_off,
+                                                       const u32* __restrict__ out_cap, MsgCols mc, BlockCols c,
+                                                       u64* lengths, i32* status) {
+  const u32 m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const u32 lane = threadIdx.x & 63;
+  if (m >= n_msgs || mc.route[m] != kRouteNoSizeFast) return;
+  const u32 first = mc.first[m], nb = mc.nb[m];
+  u64 total = 0;
+  bool bad = false;
+  for (u32 k0 = 0; k0 < nb; k0 += 64) {
+    const bool valid = k0 + lane < nb;
+    const u32 e = first + k0 + lane;
+    const bool failed = valid && (c.flags[e] & kBlkFailed);
+    const u32 len = valid && !failed ? c.out_len[e] : 0u;
+    bad = bad || __ballot(failed) != 0;
+    total += __shfl(wave_scan(len), 63, 64);
+  }
+  if (lengths) {
+    if (lane == 0) {
+      lengths[m] = bad ? 0 : total;
+      status[m] = bad ? kCorrupt : kOk;
+      mc.route[m] = kRouteDone;
+    }
+    return;
+  }
+  if (bad || total > out_cap[m]) {
+    for (u32 k = lane; k < nb; k += 64) c.flags[first + k] = 0;
+    if (lane == 0) mc.route[m] = kRouteRejected;
+    return;
+  }
+  u64 at = out_off[m];
+  for (u32 k0 = 0; k0 < nb; k0 += 64) {
+    const bool valid = k0 + lane < nb;
+    const u32 e = first + k0 + lane;
+    const u32 len = valid ? c.out_len[e] : 0u;
+    const u32 incl = wave_scan(len);
+    if (valid) {
+      c.out_off[e] = at + (incl - len);
+      c.out_cap[e] = len;
+      if (!(c.flags[e] & kBlkRaw)) c.in_len[e] = (u32)varint32_len(len) + c.src_len[e];
+    }
+    at += __shfl(incl, 63, 64);
+  }
+}
+
+// fsg_lz4f_decoded_lengths_batch, one lane per message: the stated content
+// size, or the frame's blocks listed for the length pass (linked or not:
+// lengths do not depend on linking).  A frame whose entries do not fit is
+// walked here.
+__global__ __launch_bounds__(64) void lz4f_length_index_kernel(const u8* __restrict__ in,
+                                                             const u64* __restrict__ in_off,
+                                                             const u32* __restrict__ in_len, u32 n_msgs,
+                                                             u64* __restrict__ lengths, i32* __restrict__ status,
+                                                             u32* hdr, MsgCols mc, BlockCols c, u32 nb_cap) {
+  const u32 m = blockIdx.x * 64 + threadIdx.x;
+  if (m >= n_msgs) return;
+  const u8* ib = in + in_off[m];
+  const u64 n = in_len[m];
+  lz4f::Header h;
+  mc.route[m] = kRouteDone;
+  lengths[m] = 0;
+  if (lz4f::parse_header(ib, n, &h) != lz4f::kStOk) {
+    status[m] = kBadHeader;
+    return;
+  }
+  status[m] = kOk;
+  if (h.size != lz4f::kNoSize) {
+    lengths[m] = h.size;
+    return;
+  }
+  u32 nb, xxh;
+  u64 need;
+  if (!walk_blocks(ib, n, h, true, &nb, &need, &xxh)) {
+    status[m] = kCorrupt;
+    return;
+  }
+  if (nb == 0) return;
+  const u32 base = atomicAdd(&hdr[kFdBlocks], nb);
+  if ((u64)base + nb <= nb_cap) {
+    list_unknown(ib, h, in_off[m], nb, base, 0, c);
+    mc.first[m] = base;
+    mc.nb[m] = nb;
+    mc.route[m] = kRouteNoSizeFast;
+    return;
+  }
+  const u32 bsum = (h.flg & lz4f::kFlgBlockSum) ? 4 : 0;
+  u64 ip = h.len, total = 0;
+  for (u32 k = 0; k < nb; ++k) {
+    const u32 word = lz4f::rd32(ib + ip);
+    const u32 sz = word & ~lz4f::kRawBit;
+    ip += 4;
+    u64 len = sz;
+    if (!(word & lz4f::kRawBit) && !lz4f::block_length(ib + ip, sz, h.block_max, &len)) {
+      status[m] = kCorrupt;
+      return;
+    }
+    total += len;
+    ip += sz + bsum;
+  }
+  lengths[m] = total;
 }
 
 // One wave per listed block: a compressed block becomes a body of the block
@@ -404,7 +649,7 @@ __global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ 
   if (route == kRouteDone) return;
   const u8* ib = in + in_off[m];
   u8* ob = out + out_off[m];
-  u32 blocks = 0, sums = 0;
+  u32 blocks = 0, ns_blocks = 0, sums = 0;
   if (route == kRouteFast) {
     const u32 first = mc.first[m], nb = mc.nb[m];
     bool ok = true;
@@ -422,8 +667,28 @@ __global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ 
     } else {
       route = kRouteRejected;
     }
+  } else if (route == kRouteNoSizeFast) {
+    // the blocks lie end to end from the slot's start: decoded exactly the
+    // lengths the walk found, and the checksum over them
+    const u32 first = mc.first[m], nb = mc.nb[m], last = first + nb - 1;
+    bool ok = true;
+    for (u32 k = 0; k < nb && ok; ++k) ok = !(c.flags[first + k] & kBlkFailed);
+    const u32 total = (u32)(c.out_off[last] + c.out_cap[last] - out_off[m]);
+    lz4f::Header h;
+    lz4f::parse_header(ib, in_len[m], &h);
+    if (ok && (h.flg & lz4f::kFlgSum)) {
+      ok = lz4f::xxh32(ob, total) == mc.xxh[m];
+      sums = 1;
+    }
+    if (ok) {
+      out_len[m] = total;
+      status[m] = kOk;
+      ns_blocks = nb;
+    } else {
+      route = kRouteRejected;
+    }
   }
-  if (route != kRouteFast) {
+  if (route != kRouteFast && route != kRouteNoSizeFast) {
     u32 ol, s = 0;
     status[m] = lz4f::decode_frame(ib, in_len[m], ob, out_cap[m], &ol, &s);
     out_len[m] = ol;
@@ -436,6 +701,10 @@ __global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ 
   count_lanes(&hdr[kFdForced], route == kRouteForced);
   if (blocks) atomicAdd(&hdr[kFdFastBlocks], blocks);
   if (sums) atomicAdd(&hdr[kFdSums], sums);
+  if (ns_blocks) {  // (no frame is on this route unless the option is set)
+    atomicAdd(&hdr[kFdNsMsgs], 1u);
+    atomicAdd(&hdr[kFdNsBlocks], ns_blocks);
+  }
 }
 
 // ---- workspace layouts
@@ -556,8 +825,10 @@ void lz4f_encode_header_counts(const void* header, Lz4fEncodeHeaderCounts* c) {
   c->overflow_messages = ctr[kFcOverflow];
 }
 void lz4f_decode_header_counts(const void* header, Lz4fDecodeHeaderCounts* c) {
-  u32 ctr[12];
+  u32 ctr[14];
   __builtin_memcpy(ctr, header, sizeof(ctr));
+  c->fast_nosize_messages = ctr[kFdNsMsgs];
+  c->fast_nosize_blocks = ctr[kFdNsBlocks];
   c->fast_messages = ctr[kFdFastMsgs];
   c->fast_blocks = ctr[kFdFastBlocks];
   c->empty_messages = ctr[kFdEmpty];
@@ -609,9 +880,58 @@ hipError_t launch_lz4f_content_sizes(const u8* in, const u64* in_off, const u32*
   return hipGetLastError();
 }
 
+namespace {
+// the length pass on the claimed entries: lanes, then the listed large blocks
+// (a grid of 256 blocks: with none listed each wave reads the count and leaves)
+hipError_t launch_length_pass(const u8* in, u32* hdr, const BlockCols& c, u32 nb_cap, u32 wave_min,
+                              hipStream_t stream) {
+  const u32 grid = (nb_cap + 63) / 64 < 4096 ? (nb_cap + 63) / 64 : 4096;
+  lz4f_length_lane_kernel<<<grid, 64, 0, stream>>>(in, hdr, c, nb_cap, wave_min);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  lz4f_length_wave_kernel<<<256, kLenWaves * 64, 0, stream>>>(in, hdr, c);
+  return hipGetLastError();
+}
+}  // namespace
+
+// The wave threshold of the length pass from option lz4f_length_wave_min.
+// Automatic: 2 KiB whatever the batch.  Measured on MI355X (DESIGN.md section
+// 5, "LZ4 frames without a content size", the lane-against-wave table): the
+// wave won at every point, from 1.14x (4,096 blocks of 4 KiB, 2.7 KB stored)
+// to 10.7x (64 blocks of 4 MiB); the smallest stored size in the table is
+// 2.7 KB and nothing below it was measured, so blocks of at most 2 KiB stay
+// with the lanes.  (The first build took the block decoder's rule, 2 KiB up
+// to 256 block entries and 64 KiB above; the table did not bear out the 64
+// KiB.)
+u32 lz4f_length_wave_min(i64 option) {
+  if (option < 0) return 2048u;
+  return option >= 0xFFFFFFFFll ? 0xFFFFFFFFu : (u32)option;
+}
+
+hipError_t launch_lz4f_decoded_lengths(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* lengths,
+                                       i32* status, void* ws, size_t ws_bytes, u32 length_wave_min,
+                                       hipStream_t stream) {
+  if (n_msgs == 0) return hipSuccess;
+  Plan p;
+  if (!plan_for(ws_bytes, &p, [&](u64 t, Plan* q) { return dec_plan(n_msgs, t, q); })) return hipErrorInvalidValue;
+  u8* const w = static_cast<u8*>(ws);
+  u32* const hdr = reinterpret_cast<u32*>(w);
+  const MsgCols mc = msg_cols(w + p.off_msg, n_msgs);
+  const BlockCols c = block_cols(w + p.off_blk, p.nb_cap);
+  hipError_t e = hipMemsetAsync(w, 0, p.off_dummy, stream);
+  if (e != hipSuccess) return e;
+  lz4f_length_index_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, lengths, status, hdr, mc,
+                                                                 c, p.nb_cap);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = launch_length_pass(in, hdr, c, p.nb_cap, length_wave_min, stream)) != hipSuccess) return e;
+  lz4f_place_kernel<<<(n_msgs + 3) / 4, 256, 0, stream>>>(n_msgs, nullptr, nullptr, mc, c, lengths, status);
+  return hipGetLastError();
+}
+
 hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
-                              size_t ws_bytes, bool force_serial, hipStream_t stream) {
+                              size_t ws_bytes, bool force_serial, bool nosize_fast, u32 length_wave_min,
+                              hipStream_t stream) {
   if (n_msgs == 0) return hipSuccess;
   Plan p;
   if (!plan_for(ws_bytes, &p, [&](u64 t, Plan* q) { return dec_plan(n_msgs, t, q); })) return hipErrorInvalidValue;
@@ -625,9 +945,14 @@ hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len
   if (e != hipSuccess) return e;
   lz4f_index_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out_off, out_cap, out_len,
                                                           status, hdr, mc, c, p.nb_cap, p.off_stage, p.stage_cap,
-                                                          force_serial ? 1u : 0u);
+                                                          force_serial ? 1u : 0u, nosize_fast ? 1u : 0u);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const u32* inner_fallback = nullptr;
+  if (!force_serial && nosize_fast) {
+    if ((e = launch_length_pass(in, hdr, c, p.nb_cap, length_wave_min, stream)) != hipSuccess) return e;
+    lz4f_place_kernel<<<(n_msgs + 3) / 4, 256, 0, stream>>>(n_msgs, out_off, out_cap, mc, c, nullptr, nullptr);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
   if (!force_serial) {
     const u32 grid = (p.nb_cap + 3) / 4 < 8192 ? (p.nb_cap + 3) / 4 : 8192;
     lz4f_stage_kernel<<<grid, 256, 0, stream>>>(in, out, w, c, p.nb_cap);

@@ -42,6 +42,8 @@ enum Opt : int {
   // LZ4 frames (lz4_frame.hip)
   kOptLz4fForceSerial,    // 1: every frame on the serial decoder
   kOptLz4fBlockWaveMin,   // the block encode's wave threshold (as lz4_encode_wave_min; -1: its automatic rule)
+  kOptLz4fNosizeFast,     // 1: frames with independent blocks and no content size on the block decoders
+  kOptLz4fLengthWaveMin,  // -1 automatic; blocks above this many bytes get their length by a wave (>= 0xFFFFFFFF: none)
   kOptCount
 };
 

@@ -119,4 +119,8 @@ int fsh_cpu_lz4f_uncompress(const uint8_t* in, size_t n, uint8_t* out, size_t ca
   return kCode[flare::lz4::cpu::DecompressFrame(in, n, out, cap, out_len)];
 }
 
+uint64_t fsh_cpu_lz4f_decoded_length(const uint8_t* in, size_t n, int* status) {
+  return flare::lz4::cpu::FrameDecodedLength(in, n, status);
+}
+
 }  // extern "C"

@@ -65,9 +65,14 @@ bool Lz4FrameDecompress(const cord_buf& in, cord_buf* out) {
   const uint64_t size = lz4::cpu::FrameContentSize(frame.data(), n, &st);
   if (st != 0) return false;
   // the size comes from the peer: bound it by what the bytes can hold before
-  // allocating; a frame without one gets the most its bytes can decode to
+  // allocating; a frame without one gets what its blocks' sequences add up to
+  // (a frame for which that walk fails does not decode either)
   if (size != ~0ull && !lz4::cpu::PlausibleLength(size, n)) return false;
-  const uint64_t cap = size != ~0ull ? size : 255ull * n + 64;
+  uint64_t cap = size;
+  if (size == ~0ull) {
+    cap = lz4::cpu::FrameDecodedLength(frame.data(), n, &st);
+    if (st != 0) return false;
+  }
   if (cap > 0xFFFFFFFFull) return false;
   std::vector<uint8_t> raw(cap);
   uint32_t len = 0;

@@ -53,5 +53,13 @@ size_t CompressFrame(const uint8_t* in, size_t n, uint8_t* out, int block_size_i
 int DecompressFrame(const uint8_t* in, size_t n, uint8_t* out, size_t cap, uint32_t* out_len);
 // The descriptor's content size (~0 when it states none); *status 0 or 2.
 uint64_t FrameContentSize(const uint8_t* in, size_t n, int* status);
+// The decoded length of a frame as fsg_lz4f_decoded_lengths_batch gives it:
+// the stated content size, or for a frame that states none the sum of its
+// blocks' decoded lengths (lz4f::block_length; a raw block's stored size),
+// linked blocks or not.  *status 0, 2 (bad header) or 1 (broken block
+// structure, a block without a length; the result is 0).  No checksum is
+// looked at and nothing is decoded: status 0 does not promise that the frame
+// decodes.
+uint64_t FrameDecodedLength(const uint8_t* in, size_t n, int* status);
 
 }  // namespace flare::lz4::cpu

@@ -46,7 +46,8 @@ Lz4fEncodeReport = _report_struct("Lz4fEncodeReport", (
     "blocks", "raw_blocks", "overflow_messages", "block_entries", "block_wave_min"))
 Lz4fDecodeReport = _report_struct("Lz4fDecodeReport", (
     "fast_messages", "fast_blocks", "empty_messages", "serial_linked", "serial_no_size", "serial_rejected",
-    "serial_forced", "checksummed_units", "inner_fallback_blocks", "block_entries"))
+    "serial_forced", "checksummed_units", "inner_fallback_blocks", "block_entries", "fast_nosize_messages",
+    "fast_nosize_blocks"))
 LZ4F_NO_CONTENT_SIZE = 0xFFFFFFFFFFFFFFFF
 PATH_MAIN, PATH_SINGLE_DESIGN, PATH_NO_WORKSPACE, PATH_FORCED = 0, 1, 2, 3
 
@@ -94,6 +95,7 @@ _SIGS = {
     "fsg_lz4f_decompress_workspace_bytes": (_sz, [_u32, _u64]),
     "fsg_lz4f_decompress_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "fsg_lz4f_content_sizes_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "fsg_lz4f_decoded_lengths_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _sz, _vp]),
     "fsg_lz4f_compress_report": (_c.c_int, [_vp, _u32, _sz, _u32, _c.POINTER(Lz4fEncodeReport)]),
     "fsg_lz4f_decompress_report": (_c.c_int, [_vp, _u32, _sz, _c.POINTER(Lz4fDecodeReport)]),
 }
@@ -114,7 +116,7 @@ _OPTIONAL = {"fsg_decompress_batch_2s", "fsg_decompress_batch_partial", "fsg_dec
              "fsg_compress_report", "fsg_lz4_decompress_report", "fsg_lz4_compress_report",
              "fsg_lz4f_max_frame_length", "fsg_lz4f_compress_workspace_bytes", "fsg_lz4f_compress_batch",
              "fsg_lz4f_decompress_workspace_bytes", "fsg_lz4f_decompress_batch", "fsg_lz4f_content_sizes_batch",
-             "fsg_lz4f_compress_report", "fsg_lz4f_decompress_report"}
+             "fsg_lz4f_compress_report", "fsg_lz4f_decompress_report", "fsg_lz4f_decoded_lengths_batch"}
 
 
 def load_gpu_lib(path: Path | None = None) -> ctypes.CDLL:
@@ -328,6 +330,15 @@ class SnappyGPU:
         self._check(self.lib.fsg_lz4f_content_sizes_batch(
             _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_content_size), _ptr(d_status),
             self._stream(stream)), "fsg_lz4f_content_sizes_batch")
+
+    def lz4f_decoded_lengths(self, d_in, d_in_off, d_in_len, n, d_length, d_status, workspace, stream=None):
+        """fsg_lz4f_decoded_lengths_batch on a decompress workspace (d_length
+        int64 / uint64): the content size, or the sum of the blocks' decoded
+        lengths for a frame that states none."""
+        ws = 0 if workspace is None else workspace.numel() * workspace.element_size()
+        self._check(self.lib.fsg_lz4f_decoded_lengths_batch(
+            _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_length), _ptr(d_status), _ptr(workspace), ws,
+            self._stream(stream)), "fsg_lz4f_decoded_lengths_batch")
 
     def lz4f_compress_report(self, workspace, n, block_size_id=4) -> dict:
         head, nbytes = self._report_header(workspace)

@@ -194,7 +194,26 @@ int fsg_lz4_compress_report(const void *header_host_copy, uint32_t n_msgs,
  * Linked blocks, frames without a content size, and every frame the fast route
  * does not accept (a short block in the middle, a block that fails) go to a
  * serial decoder, one lane per message, which alone decides their verdict:
- * correct and slow.  The lz4 command's default output is such a frame.
+ * correct and slow.  The lz4 command's default output is a frame without a
+ * content size, and so is LZ4F_compressFrame's when contentSize is left 0.
+ *
+ * With option lz4f_nosize_fast (FSG_L4F_NOSIZE_FAST) = 1 (default 0) a frame
+ * with independent blocks, no content size and at least one block takes a
+ * second fast route.  Its block structure is checked from the size words (no
+ * size 0, none above the block maximum, every block with its checksum inside
+ * the input, end mark, content checksum when flagged, nothing after the
+ * frame); a length pass finds every block's decoded length from its sequences
+ * (a raw block's is its stored size), one lane per block, or one wave for a
+ * block above option lz4f_length_wave_min (FSG_L4F_LENGTH_WAVE_MIN) bytes:
+ * -1 automatic (2 KiB: the wave won at every measured block size and batch,
+ * DESIGN.md section 5), 0 every compressed block by wave, >= 0xFFFFFFFF none; a prefix sum over the
+ * lengths places the blocks in the slot, and the block decoder runs them side
+ * by side.  Short blocks in the middle (LZ4F_compressUpdate with flushes) are
+ * no obstacle on this route, and d_out_cap[i] may exceed the decoded length.
+ * A frame that fails the structure check, does not fit the workspace, has a
+ * block without a length, decodes to more than d_out_cap[i], or has a block or
+ * a checksum that fails goes to the serial decoder, so the route never changes
+ * a byte or a status.  Linked frames stay serial.
  *
  * "What a *_batch call writes" holds for both calls, every status and route.
  * Slots: fsg_lz4f_max_frame_length(d_in_len[i], id) for compress. */
@@ -239,7 +258,7 @@ size_t fsg_lz4f_decompress_workspace_bytes(uint32_t n_msgs, uint64_t total_in_by
 
 /* Batched frame decompress, columns as fsg_lz4_decompress_batch_ws.  Option
  * lz4f_force_serial (FSG_L4F_FORCE_SERIAL) = 1 sends every frame to the serial
- * decoder.  A NULL workspace or one below
+ * decoder; lz4f_nosize_fast and lz4f_length_wave_min: "Routes" above.  A NULL workspace or one below
  * fsg_lz4f_decompress_workspace_bytes(n_msgs, 0) is FSG_ERR_INVALID_ARG;
  * n_msgs == 0 succeeds and launches nothing. */
 int fsg_lz4f_decompress_batch(const uint8_t *d_in, const uint64_t *d_in_off,
@@ -258,6 +277,30 @@ int fsg_lz4f_content_sizes_batch(const uint8_t *d_in, const uint64_t *d_in_off,
                                  const uint32_t *d_in_len, uint32_t n_msgs,
                                  uint64_t *d_content_size, int32_t *d_status,
                                  void *stream);
+
+/* The decoded length of each body's frame, for sizing slots when a frame
+ * states no content size: d_length[i] = the stated content size when there is
+ * one; otherwise the sum of the blocks' decoded lengths (a raw block's stored
+ * size, a compressed block's length from its sequences: the sequence whose
+ * literals end at the block's last byte ends it), whether the blocks are
+ * linked or not; 0 for a frame without blocks.  d_status[i]: FSG_OK;
+ * FSG_BAD_HEADER by the rule of the decompress call; FSG_CORRUPT (d_length[i]
+ * = 0) for a frame without a content size whose block structure is broken (a
+ * size word above the block maximum, input that ends early, no end mark,
+ * bytes after the frame) or that has a block whose sequences give no length
+ * or more than the block maximum.  Block and content checksums are not looked
+ * at, no block is decoded, and a stated content size is not checked against
+ * anything: FSG_OK does NOT promise that the frame decodes, only that a slot
+ * of d_length[i] bytes is large enough if it does.  The call takes a
+ * decompress workspace (fsg_lz4f_decompress_workspace_bytes; NULL or below
+ * that function's value for (n_msgs, 0) is FSG_ERR_INVALID_ARG) and runs the
+ * index and length kernels of the decompress call on it; a frame whose blocks
+ * do not fit the workspace is walked by one lane, with the same answer. */
+int fsg_lz4f_decoded_lengths_batch(const uint8_t *d_in, const uint64_t *d_in_off,
+                                   const uint32_t *d_in_len, uint32_t n_msgs,
+                                   uint64_t *d_length, int32_t *d_status,
+                                   void *d_workspace, size_t workspace_bytes,
+                                   void *stream);
 
 /* Path reports ("Path reports" in flare_snappy_gpu.h: host code, from a host
  * copy of the workspace's first 256 bytes taken after the call completed,
@@ -278,12 +321,14 @@ struct fsg_lz4f_decode_report {
   uint64_t fast_blocks;        /* their blocks */
   uint64_t empty_messages;     /* frames without blocks, finished by the index pass */
   uint64_t serial_linked;      /* serial route: linked blocks */
-  uint64_t serial_no_size;     /* serial route: no content size */
-  uint64_t serial_rejected;    /* serial route: the fast route did not accept the frame */
+  uint64_t serial_no_size;     /* serial route: no content size (option lz4f_nosize_fast 0) */
+  uint64_t serial_rejected;    /* serial route: a fast route, with or without a content size, did not accept the frame */
   uint64_t serial_forced;      /* serial route: option lz4f_force_serial */
   uint64_t checksummed_units;  /* block and content checksums computed */
   uint64_t inner_fallback_blocks; /* blocks the block decoder's one-pass kernel finished */
   uint64_t block_entries;      /* blocks the workspace holds */
+  uint64_t fast_nosize_messages; /* answered by the fast route for frames without a content size (FSG_OK) */
+  uint64_t fast_nosize_blocks;   /* their blocks */
 };
 int fsg_lz4f_decompress_report(const void *header_host_copy, uint32_t n_msgs,
                                size_t workspace_bytes,

@@ -117,6 +117,12 @@ size_t fsh_cpu_lz4f_compress(const uint8_t* in, size_t n, uint8_t* out, int bloc
 /* frame to out (cap bytes): 1 ok, 0 corrupt, -1 bad header, -2 content size
  * above cap; *out_len = decoded length (ok) or min(content size, 2^32-1) (-2) */
 int fsh_cpu_lz4f_uncompress(const uint8_t* in, size_t n, uint8_t* out, size_t cap, uint32_t* out_len);
+/* decoded length of a frame without decoding it: the stated content size, or
+ * the sum of its blocks' lengths when it states none; *status 0 ok, 1 corrupt
+ * (returns 0), 2 bad header (returns 0): the FSG_* status words, as
+ * fsg_lz4f_decoded_lengths_batch.  No checksum is looked at: status 0 does not
+ * promise that the frame decodes. */
+uint64_t fsh_cpu_lz4f_decoded_length(const uint8_t* in, size_t n, int* status);
 
 #ifdef __cplusplus
 }

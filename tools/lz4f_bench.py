@@ -6,12 +6,22 @@ launch stream after warm-up launches of both; the median, minimum and maximum
 per call.  One JSON line per row.
 
     python tools/lz4f_bench.py [--rows 16x4m,c3] [--launches 7] [--warmup 2] [--bid 4]
+    python tools/lz4f_bench.py --no-size [--rows 16x4m@7,16x4m@7c,c3,1x64k] [--bid 4] [--checksum 1]
+    python tools/lz4f_bench.py --length-pass
 
 Rows: 16x4m (16 x 4 MiB: 64 independent blocks a body, where the format adds
 parallelism) and c3 (65,536 x 64 KiB: one block a body, the cost of the plan,
 stage, assemble and finish passes).  Round trips are checked untimed, frames of
 a sample against the frame oracle.  `staging_bytes`: what the decompressor's
 stage pass copies (one read and one write of the compressed blocks).
+
+--no-size: the rows' frames with the content size field taken out (what the
+lz4 command and LZ4F_compressFrame with contentSize 0 write) through
+fsg_lz4f_decompress_batch with option lz4f_nosize_fast at 0 (the serial
+decoder) and at 1 (the block decoders), alternating; a library without the
+option gives the serial figure alone.  --length-pass: the length pass by
+itself (fsg_lz4f_decoded_lengths_batch on one-block frames without a content
+size), one lane per block against one wave per block, by block size and batch.
 """
 import argparse
 import json
@@ -25,7 +35,8 @@ for p in (REPO / "flare-cpp_amd" / "py", REPO / "oracle", REPO / "tests"):
     sys.path.insert(0, str(p))
 import fsg  # noqa: E402
 
-ROWS = {"16x4m": (16, 4 << 20), "c3": (65536, 64 << 10), "256x256k": (256, 256 << 10)}
+ROWS = {"16x4m": (16, 4 << 20), "c3": (65536, 64 << 10), "256x256k": (256, 256 << 10), "1x64k": (1, 64 << 10)}
+NONE = 0xFFFFFFFF
 
 
 def stats(ms):
@@ -120,9 +131,142 @@ def row(torch, codec, name, bid, warmup, launches):
     print(json.dumps(out), flush=True)
 
 
+def has_option(name):
+    try:
+        fsg.get_option(name)
+        return True
+    except Exception:
+        return False
+
+
+def nosize_frames(torch, codec, batch, bid, checksum):
+    """(bytes, offsets, lengths as host arrays) of the batch's frames without
+    a content size: compressed on the device, the 8-byte field cut out and the
+    descriptor's check byte made right on the host."""
+    import lz4f_ref
+    dev = torch.device("cuda", 0)
+    lib = codec.lib
+    n = len(batch)
+    H = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    f_off, f_tot = fsg.slot_offsets(np.array([lib.fsg_lz4f_max_frame_length(int(x), bid) for x in batch.lens], np.uint64))
+    d_f = torch.zeros(f_tot, dtype=torch.uint8, device=dev)
+    d_fl = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+    ws = codec.lz4f_compress_workspace(n, batch.total, bid)
+    codec.lz4f_compress(H(batch.data), H(batch.offsets), H(batch.lens), n, d_f, H(f_off), d_fl, d_st, ws,
+                        block_size_id=bid, checksum=checksum)
+    torch.cuda.synchronize()
+    assert int((d_st != 0).sum().item()) == 0
+    host = d_f.cpu().numpy()
+    flen = d_fl.cpu().numpy().view(np.uint32).astype(np.uint64)
+    lens = (flen - 8).astype(np.uint32)
+    offs, total = fsg.slot_offsets(lens.astype(np.uint64))
+    out = np.zeros(total, np.uint8)
+    for i in range(n):
+        a, b = int(f_off[i]), int(offs[i])
+        head = bytes(host[a:a + 6])
+        assert head[4] & lz4f_ref.F_SIZE
+        d = bytes([head[4] & ~lz4f_ref.F_SIZE, head[5]])
+        out[b:b + 4] = host[a:a + 4]
+        out[b + 4:b + 7] = np.frombuffer(d + bytes([(lz4f_ref.xxh32(d) >> 8) & 0xFF]), np.uint8)
+        out[b + 7:b + int(lens[i])] = host[a + 15:a + int(flen[i])]
+    return out, offs, lens
+
+
+def nosize_row(torch, codec, name, bid, checksum, warmup, launches):
+    dev = torch.device("cuda", 0)
+    n, size = ROWS[name]
+    batch = fsg.make_batch(fsg.KIND_TEXT, np.full(n, size, np.uint32))
+    H = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    s = torch.cuda.current_stream()
+    data, offs, lens = nosize_frames(torch, codec, batch, bid, checksum)
+    torch.cuda.empty_cache()
+    d_f, d_fo, d_fl = H(data), H(offs), H(lens)
+    d_raw, d_ro, d_rl = H(batch.data), H(batch.offsets), H(batch.lens)
+    d_out = torch.full((batch.total,), 0xA5, dtype=torch.uint8, device=dev)
+    d_ol = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+    ws = codec.lz4f_decompress_workspace(n, int(data.size))
+    routed = has_option("lz4f_nosize_fast")
+    out = {"mode": "no_size", "row": name, "n": n, "size": size, "block_size_id": bid, "checksum": int(checksum),
+           "launches": launches, "warmup": warmup, "raw_bytes": batch.total, "frame_bytes": int(lens.sum()),
+           "has_option": routed}
+
+    def call(fast):
+        def fn():
+            if routed:
+                fsg.set_option("lz4f_nosize_fast", fast)
+            codec.lz4f_decompress(d_f, d_fo, d_fl, n, d_out, d_ro, d_rl, d_ol, d_st, ws, stream=s)
+        return fn
+
+    def check():
+        return int((d_st != 0).sum().item()) == 0 and bool(torch.equal(d_out, d_raw))
+
+    if routed:
+        saved = fsg.get_option("lz4f_nosize_fast")
+        ms = alternate(torch, s, (call(0), call(1)), warmup, launches)
+        out["serial_call"], out["fast_call"] = ms
+        out["gain"] = round(ms[0]["median_ms"] / ms[1]["median_ms"], 3)
+        d_out.fill_(0xA5)
+        call(1)()
+        torch.cuda.synchronize()
+        out["fast_ok"] = check()
+        out["fast_report"] = codec.lz4f_decompress_report(ws, n)
+        length_mode = fsg.get_option("lz4f_length_wave_min")
+        out["length_wave_min_option"] = length_mode
+        d_out.fill_(0xA5)
+        call(0)()
+        torch.cuda.synchronize()
+        out["serial_ok"] = check()
+        fsg.set_option("lz4f_nosize_fast", saved)
+    else:
+        out["serial_call"] = alternate(torch, s, (call(0),), warmup, launches)[0]
+        out["serial_ok"] = check()
+    out["serial_report"] = codec.lz4f_decompress_report(ws, n)
+    print(json.dumps(out), flush=True)
+
+
+def length_pass(torch, codec, warmup, launches, limit_bytes=2 << 30):
+    """Lane against wave for the length pass alone."""
+    dev = torch.device("cuda", 0)
+    H = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    s = torch.cuda.current_stream()
+    saved = fsg.get_option("lz4f_length_wave_min")
+    for size in (4 << 10, 16 << 10, 64 << 10, 256 << 10, 1 << 20, 4 << 20):
+        for count in (1, 64, 4096):
+            if size * count > limit_bytes:
+                print(json.dumps({"mode": "length_pass", "block_bytes": size, "blocks": count, "skipped": "too large"}),
+                      flush=True)
+                continue
+            batch = fsg.make_batch(fsg.KIND_TEXT, np.full(count, size, np.uint32))
+            data, offs, lens = nosize_frames(torch, codec, batch, 7, False)
+            d_f, d_fo, d_fl = H(data), H(offs), H(lens)
+            d_len = torch.zeros(count, dtype=torch.int64, device=dev)
+            d_st = torch.zeros(count, dtype=torch.int32, device=dev)
+            ws = codec.lz4f_decompress_workspace(count, int(data.size))
+
+            def call(wave_min):
+                def fn():
+                    fsg.set_option("lz4f_length_wave_min", wave_min)
+                    codec.lz4f_decoded_lengths(d_f, d_fo, d_fl, count, d_len, d_st, ws, stream=s)
+                return fn
+            ms = alternate(torch, s, (call(NONE), call(0)), warmup, launches)
+            ok = int((d_st != 0).sum().item()) == 0 and bool((d_len == size).all().item())
+            print(json.dumps({"mode": "length_pass", "block_bytes": size, "blocks": count,
+                              "stored_bytes_mean": int(lens.mean()) - 15, "lane_call": ms[0], "wave_call": ms[1],
+                              "lane_over_wave": round(ms[0]["median_ms"] / ms[1]["median_ms"], 3), "ok": ok}),
+                  flush=True)
+            del d_f, ws
+            torch.cuda.empty_cache()
+    fsg.set_option("lz4f_length_wave_min", saved)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", default="16x4m,c3")
+    ap.add_argument("--no-size", action="store_true", help="frames without a content size: serial against routed")
+    ap.add_argument("--checksum", type=int, default=0, help="--no-size: frames with a content checksum")
+    ap.add_argument("--length-pass", action="store_true", help="the length pass alone: lane against wave")
     ap.add_argument("--bid", type=int, default=4, help="block size id 4..7")
     ap.add_argument("--launches", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
@@ -131,8 +275,16 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("lz4f_bench needs a GPU")
     codec = fsg.SnappyGPU(0)
+    if a.length_pass:
+        length_pass(torch, codec, a.warmup, a.launches)
+        return
     for name in a.rows.split(","):
-        row(torch, codec, name, a.bid, a.warmup, a.launches)
+        if a.no_size:  # row[@id[c]]: a block size id and a content checksum of the row's own
+            name, _, spec = name.partition("@")
+            bid = int(spec.rstrip("c")) if spec.rstrip("c") else a.bid
+            nosize_row(torch, codec, name, bid, spec.endswith("c") or bool(a.checksum), a.warmup, a.launches)
+        else:
+            row(torch, codec, name, a.bid, a.warmup, a.launches)
         torch.cuda.empty_cache()
 
 
