@@ -55,6 +55,7 @@ constexpr OptDesc kOptDesc[fsg::kOptCount] = {
     {"lz4f_block_wave_min", "FSG_L4F_BLOCK_WAVE_MIN", -1},
     {"lz4f_nosize_fast", "FSG_L4F_NOSIZE_FAST", 0},
     {"lz4f_length_wave_min", "FSG_L4F_LENGTH_WAVE_MIN", -1},
+    {"lz4f_linked_fast", "FSG_L4F_LINKED_FAST", 0},
 };
 // DecodeOpts' initialisers (decode_v4_plan.h, which the CPU test of the launch
 // plan uses as "the defaults") are this table's
@@ -631,6 +632,7 @@ int fsg_lz4f_decompress_batch(const uint8_t* d_in, const uint64_t* d_in_off, con
                                         d_status, d_workspace, workspace_bytes,
                                         fsg::opt(fsg::kOptLz4fForceSerial) != 0,
                                         fsg::opt(fsg::kOptLz4fNosizeFast) != 0,
+                                        fsg::opt(fsg::kOptLz4fLinkedFast) != 0,
                                         fsg::lz4f_length_wave_min(fsg::opt(fsg::kOptLz4fLengthWaveMin)),
                                         (hipStream_t)stream),
                 "fsg_lz4f_decompress_batch");
@@ -694,6 +696,8 @@ int fsg_lz4f_decompress_report(const void* header_host_copy, uint32_t n_msgs, si
   out->inner_fallback_blocks = c.inner_fallback;
   out->fast_nosize_messages = c.fast_nosize_messages;
   out->fast_nosize_blocks = c.fast_nosize_blocks;
+  out->fast_linked_messages = c.fast_linked_messages;
+  out->fast_linked_blocks = c.fast_linked_blocks;
   return FSG_SUCCESS;
 }
 

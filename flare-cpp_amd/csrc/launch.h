@@ -75,9 +75,28 @@ hipError_t launch_lz4_decode_fallback(const u8* in, const u64* in_off, const u32
                                       u32* fb_count, hipStream_t stream);
 size_t lz4_decode_workspace_bytes(u32 n_msgs, u64 total_in_bytes);
 u64 lz4_decode_bitmap_capacity_words(u32 n_msgs, size_t ws_bytes);
+// Entries that continue earlier output (the blocks of a linked LZ4 frame).
+// word[e] >> shift bytes directly below entry e's slot are its history: the
+// index passes accept offsets into them.  An entry with a bit of chained_mask
+// is executed by its chain's wave, not by the execution pass: chain c is the
+// entries first[c] .. first[c] + count[c], run in order by one wave when
+// (state[c] & ~pending_mask) == pending; entries with a bit of skip_mask are
+// passed over.  The wave stops at the first entry the index pass did not
+// answer FSG_OK, and adds done_add to state[c] only when it ran to the end.
+struct Lz4Chains {
+  const u32* word;
+  u32 shift, chained_mask, skip_mask;
+  u32 n_chains;
+  const u32* first;
+  const u32* count;
+  u32* state;
+  u32 pending, pending_mask, done_add;
+};
+// chains = nullptr: no entry has a prefix (the forms of the kernels without one)
 hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
-                              size_t ws_bytes, hipStream_t stream, hipStream_t pass1_stream);
+                              size_t ws_bytes, hipStream_t stream, hipStream_t pass1_stream,
+                              const Lz4Chains* chains = nullptr);
 
 // ---- LZ4 frames (lz4_frame.hip; include/flare_lz4_gpu.h, "LZ4 frames").  The
 // calls get no input size: the workspace says what it was sized for, and the
@@ -91,8 +110,8 @@ hipError_t launch_lz4f_encode(const u8* in, const u64* in_off, const u32* in_len
                               size_t ws_bytes, u64 wave_min, hipStream_t stream);
 hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
-                              size_t ws_bytes, bool force_serial, bool nosize_fast, u32 length_wave_min,
-                              hipStream_t stream);
+                              size_t ws_bytes, bool force_serial, bool nosize_fast, bool linked_fast,
+                              u32 length_wave_min, hipStream_t stream);
 // the length pass's wave threshold from option lz4f_length_wave_min (-1: the automatic rule)
 u32 lz4f_length_wave_min(i64 option);
 // fsg_lz4f_decoded_lengths_batch: on a decompress workspace
@@ -125,6 +144,7 @@ struct Lz4fDecodeHeaderCounts {
   u32 serial_linked, serial_no_size, serial_rejected, serial_forced;
   u32 checksummed_units, inner_fallback;
   u32 fast_nosize_messages, fast_nosize_blocks;
+  u32 fast_linked_messages, fast_linked_blocks;
 };
 void lz4f_encode_header_counts(const void* header, Lz4fEncodeHeaderCounts* c);
 void lz4f_decode_header_counts(const void* header, Lz4fDecodeHeaderCounts* c);

@@ -41,6 +41,14 @@
 //
 // Messages whose bitmap does not fit the workspace get kNeedFallback and are
 // decoded by lz4.hip's lane-per-message kernel.
+//
+// Linked LZ4 frame blocks (launch.h, Lz4Chains; lz4_frame.hip): a message may
+// begin with a prefix, bytes of history directly below its slot.  The kernels
+// are templates on that; without chains the launch takes the forms without a
+// prefix, whose instructions are those of the kernels before the templates.
+// Pass 1 needs only the prefix's length, so it still runs on every message at
+// once; the messages of a chain are executed in order by one wave,
+// lz4_exec_chain_kernel.
 #include <cstdlib>
 #include <mutex>
 
@@ -143,11 +151,20 @@ __device__ __forceinline__ u32 mux4(u32 d0, u32 d1, u32 d2, u32 d3, u32 i) {
   return (i & 2) ? b : a;
 }
 
+//
+// kPrefix (linked frame blocks): message m has pfx = prefix[m] >> pshift bytes
+// of history directly below its slot.  The walk is that of a message of
+// pfx + ulen output bytes standing at op = pfx: every offset check then
+// accepts exactly the offsets that stay inside the history, a first sequence
+// without literals included, and the end rules, which only see ulen - op, are
+// the block's own.  out_len stays the block's length.
+template <bool kPrefix>
 __global__ __launch_bounds__(64) void lz4_index_kernel(
     const u8* __restrict__ in, const u64* __restrict__ in_off, const u32* __restrict__ in_len, u32 n_msgs,
     const u32* __restrict__ out_cap, u32* __restrict__ out_len, i32* __restrict__ status_out,
     u32* __restrict__ bm_counter, u32* __restrict__ bm_base_out, u32* __restrict__ hdr_out,
-    u32* __restrict__ bitmap, u64 bm_capacity_words, u32* __restrict__ big_list, u32 big_min) {
+    u32* __restrict__ bitmap, u64 bm_capacity_words, u32* __restrict__ big_list, u32 big_min,
+    const u32* __restrict__ prefix, u32 pshift) {
   // [dword][lane]; rows kL4RingDwords.. +3 repeat rows 0..3 (a 5-dword read
   // at the ring's end wraps)
   __shared__ u32 ring[(kL4RingDwords + 4) * kWave];
@@ -170,6 +187,11 @@ __global__ __launch_bounds__(64) void lz4_index_kernel(
       out_len[m] = ulen;
       st = ulen > out_cap[m] ? kSlotTooSmall : kL4Parsing;
     }
+  }
+  u32 pfx = 0;
+  if constexpr (kPrefix) {
+    pfx = valid ? prefix[m] >> pshift : 0u;
+    ulen += pfx;
   }
   const u8* bb = ib + h;
   const u32 n = st < 0 ? n_in - h : 0u;  // block bytes
@@ -224,7 +246,7 @@ __global__ __launch_bounds__(64) void lz4_index_kernel(
   const u32 ngroups = words >> 2;
 
   // walk state: pos = the next token (half 0) or offset field (half 1)
-  u32 pos = 0, op = 0, nib = 0;
+  u32 pos = 0, op = pfx, nib = 0;
   bool half = false, stall = false;
   u32x4 g[kL4Ahead];
 #pragma unroll
@@ -450,12 +472,13 @@ __device__ __forceinline__ u32 window4(u64 X01, u64 X23, u64 X45, u32 k) {
   return sh ? (u32)((lo >> sh) | (hi << (64 - sh))) : (u32)lo;
 }
 
-__device__ i32 lz4_walk_big(u32 m, const u8* __restrict__ in, const u64* __restrict__ in_off,
+template <bool kPrefix>
+__device__ i32 lz4_walk_big(u32 m, u32 pfx, const u8* __restrict__ in, const u64* __restrict__ in_off,
                             const u32* __restrict__ in_len, const u32* __restrict__ out_len,
                             const u32* __restrict__ bm_base, const u32* __restrict__ hdr, u32* __restrict__ bitmap,
                             u32* ring, u32 lane) {
   const u32 h = rfl(hdr[m]);
-  const u32 ulen = rfl(out_len[m]);
+  const u32 ulen = kPrefix ? rfl(out_len[m]) + pfx : rfl(out_len[m]);  // (kPrefix: as lz4_index_kernel)
   const u32 n = rfl(in_len[m]) - h;  // > big_min > 0
   const u8* bb = in + in_off[m] + h;
   u32* bm = bitmap + rfl(bm_base[m]);
@@ -516,7 +539,7 @@ __device__ i32 lz4_walk_big(u32 m, const u8* __restrict__ in, const u64* __restr
     if (lane == 0) __hip_atomic_fetch_or(bm + (p >> 5), 1u << (p & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
 
-  u32 pos = 0, op = 0;
+  u32 pos = 0, op = kPrefix ? pfx : 0u;
   i32 status = -1;
   // One sequence at pos, wave-uniform (the lane walk's rules in order,
   // lz4o_decompress_block :168-202): returns with pos / op advanced, or
@@ -683,11 +706,12 @@ __device__ i32 lz4_walk_big(u32 m, const u8* __restrict__ in, const u64* __restr
   return status;
 }
 
+template <bool kPrefix>
 __global__ __launch_bounds__(kBigWaves * 64) void lz4_index_big_kernel(
     const u8* __restrict__ in, const u64* __restrict__ in_off, const u32* __restrict__ in_len,
     const u32* __restrict__ out_len, i32* __restrict__ status_out, u32* __restrict__ counter,
     const u32* __restrict__ big_list, const u32* __restrict__ bm_base, const u32* __restrict__ hdr,
-    u32* __restrict__ bitmap) {
+    u32* __restrict__ bitmap, const u32* __restrict__ prefix, u32 pshift) {
   __shared__ u32 ring_s[kBigWaves][kBigRingDw + 8];
   const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const u32 lane = threadIdx.x & 63;
@@ -698,24 +722,34 @@ __global__ __launch_bounds__(kBigWaves * 64) void lz4_index_big_kernel(
     const u32 idx = (u32)__builtin_amdgcn_readfirstlane((int)got);
     if (idx >= count) break;
     const u32 m = (u32)__builtin_amdgcn_readfirstlane((int)big_list[idx]);
-    const i32 st = lz4_walk_big(m, in, in_off, in_len, out_len, bm_base, hdr, bitmap, ring_s[wv], lane);
+    u32 pfx = 0;
+    if constexpr (kPrefix) pfx = rfl(prefix[m] >> pshift);
+    const i32 st = lz4_walk_big<kPrefix>(m, pfx, in, in_off, in_len, out_len, bm_base, hdr, bitmap, ring_s[wv], lane);
     if (lane == 0) status_out[m] = st;
   }
 }
 
 // ===========================================================================
 // Pass 2: execute, one wave per message.
+//
+// kPrefix (a linked frame's block, lz4_exec_chain_kernel): the pfx output
+// bytes directly below the slot are the block's history, in the slot already.
+// The message is then one of pfx + out_len bytes whose first pfx exist, and
+// the wave enters in the state a long sequence that ended at op = pfx leaves
+// behind: the window one 16-byte block below op with its head read back from
+// the slot, flushed = op.  Nothing below pfx is ever stored.
+template <bool kPrefix>
 __device__ __forceinline__ void lz4_exec_message(
-    u32 m, const u8* __restrict__ in, const u64* __restrict__ in_off, const u32* __restrict__ in_len, u8* out,
+    u32 m, u32 pfx, const u8* __restrict__ in, const u64* __restrict__ in_off, const u32* __restrict__ in_len, u8* out,
     const u64* __restrict__ out_off, const u32* __restrict__ out_len, const u32* __restrict__ bm_base,
     const u32* __restrict__ hdr, const u32* __restrict__ bitmap, u32* ring, u8* sb, const u32x4* sel_tab,
     const u32x4* mtab, u32 lane) {
   const u32 h = hdr[m];
   const u32 n = in_len[m] - h;
-  const u32 expected = out_len[m];
+  const u32 expected = kPrefix ? pfx + out_len[m] : out_len[m];
   const u32* bm = bitmap + bm_base[m];
   const u8* bb = in + in_off[m] + h;
-  u8* ob = out + out_off[m];
+  u8* ob = kPrefix ? out + out_off[m] - pfx : out + out_off[m];
   const u32 bbal = (u32)(reinterpret_cast<uintptr_t>(bb) & 15);
   const u32 obal = (u32)(reinterpret_cast<uintptr_t>(ob) & 15);
   const __amdgpu_buffer_rsrc_t irsrc = msg_rsrc(bb - bbal, bbal + n);
@@ -734,6 +768,20 @@ __device__ __forceinline__ void lz4_exec_message(
   zero_from(0);
   u32 zero_end = 1024;
   wave_lds_fence();
+  if constexpr (kPrefix) {
+    // (the first block of the buffer may begin below the history: its bytes
+    // there are never read as a source and never flushed)
+    op = flushed = pfx;
+    sbase = (int)((op + obal) & ~15u) - (int)obal - 16;
+    if (lane < 2) {
+      const int lo = sbase + 16 * (int)lane;
+      if (lo + (int)obal >= 0 && lo < (int)op) {
+        const u32 c = (int)op - lo < 16 ? (u32)((int)op - lo) : 16u;
+        store_exact(sb + 16 * lane, far_load(orsrc, (u32)(lo + (int)obal)), c);
+      }
+    }
+    wave_lds_fence();
+  }
   auto fill_word = [&](u32 sc) -> u32 {
     const u32 wi = sc + (lane >> 2);
     return (lane < 4 * kL4FillWords && wi < nwords) ? bm[wi] : 0u;
@@ -1102,10 +1150,14 @@ __device__ __forceinline__ void lz4_exec_message(
 #ifndef FSG_L4_EXEC_WAVES
 #define FSG_L4_EXEC_WAVES 7
 #endif
+// kChains: a message whose word has a bit of chained_mask belongs to a chain
+// and is left to lz4_exec_chain_kernel.
+template <bool kChains>
 __global__ __launch_bounds__(kL4Waves * 64) __attribute__((amdgpu_waves_per_eu(FSG_L4_EXEC_WAVES, FSG_L4_EXEC_WAVES))) void lz4_exec_kernel(
     const u8* __restrict__ in, const u64* __restrict__ in_off, const u32* __restrict__ in_len, u32 n_msgs,
     u8* out, const u64* __restrict__ out_off, const u32* __restrict__ out_len, const i32* __restrict__ status,
-    const u32* __restrict__ bm_base, const u32* __restrict__ hdr, const u32* __restrict__ bitmap) {
+    const u32* __restrict__ bm_base, const u32* __restrict__ hdr, const u32* __restrict__ bitmap,
+    const u32* __restrict__ word, u32 chained_mask) {
   __shared__ __attribute__((aligned(16))) u8 wl_s[kL4Waves][4 * kL4Ring + kL4Window + 32];
   __shared__ u32x4 sel_tab[16];
   __shared__ u32x4 mask_tab[17];
@@ -1116,8 +1168,51 @@ __global__ __launch_bounds__(kL4Waves * 64) __attribute__((amdgpu_waves_per_eu(F
   const u32 lane = threadIdx.x & 63;
   const u32 m = blockIdx.x * kL4Waves + wv;
   if (m >= n_msgs || status[m] != kOk || out_len[m] == 0) return;
-  lz4_exec_message(m, in, in_off, in_len, out, out_off, out_len, bm_base, hdr, bitmap,
-                   reinterpret_cast<u32*>(wl_s[wv]), wl_s[wv] + 4 * kL4Ring, sel_tab, mask_tab, lane);
+  if constexpr (kChains) {
+    if (word[m] & chained_mask) return;
+  }
+  lz4_exec_message<false>(m, 0, in, in_off, in_len, out, out_off, out_len, bm_base, hdr, bitmap,
+                          reinterpret_cast<u32*>(wl_s[wv]), wl_s[wv] + 4 * kL4Ring, sel_tab, mask_tab, lane);
+}
+
+// Linked frames: one WAVE per chain (a frame's entries first .. first + count,
+// statically mapped) executes the chain's entries in order, each with its
+// prefix, so every history byte a block reads was stored by this wave earlier
+// in program order (behind wait_all_memory) or by an earlier launch.  An entry
+// with a bit of skip_mask (a raw block, in place already) is passed over.  The
+// chain stops at the first entry pass 1 did not accept; only a chain that ran
+// to its end moves its state word from pending to pending + done_add, which is
+// what the caller must see before it believes any entry of the chain.  No wave
+// waits for another.
+__global__ __launch_bounds__(kL4Waves * 64) __attribute__((amdgpu_waves_per_eu(FSG_L4_EXEC_WAVES, FSG_L4_EXEC_WAVES))) void lz4_exec_chain_kernel(
+    const u8* __restrict__ in, const u64* __restrict__ in_off, const u32* __restrict__ in_len, u32 n_msgs,
+    u8* out, const u64* __restrict__ out_off, const u32* __restrict__ out_len, const i32* __restrict__ status,
+    const u32* __restrict__ bm_base, const u32* __restrict__ hdr, const u32* __restrict__ bitmap, Lz4Chains ch) {
+  __shared__ __attribute__((aligned(16))) u8 wl_s[kL4Waves][4 * kL4Ring + kL4Window + 32];
+  __shared__ u32x4 sel_tab[16];
+  __shared__ u32x4 mask_tab[17];
+  if (threadIdx.x < 64) init_pattern_table(sel_tab, threadIdx.x);
+  init_mask_table(mask_tab, threadIdx.x);
+  __syncthreads();
+  const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const u32 lane = threadIdx.x & 63;
+  const u32 c = blockIdx.x * kL4Waves + wv;
+  if (c >= ch.n_chains) return;
+  const u32 state = rfl(ch.state[c]);
+  if ((state & ~ch.pending_mask) != ch.pending) return;
+  const u32 first = rfl(ch.first[c]), count = rfl(ch.count[c]);
+  if (first >= n_msgs || count > n_msgs - first) return;
+  for (u32 k = 0; k < count; ++k) {
+    const u32 e = first + k;
+    const u32 w = rfl(ch.word[e]);
+    if (w & ch.skip_mask) continue;
+    if (rfl((u32)status[e]) != (u32)kOk) return;
+    if (rfl(out_len[e]) == 0) continue;
+    lz4_exec_message<true>(e, w >> ch.shift, in, in_off, in_len, out, out_off, out_len, bm_base, hdr, bitmap,
+                           reinterpret_cast<u32*>(wl_s[wv]), wl_s[wv] + 4 * kL4Ring, sel_tab, mask_tab, lane);
+    wait_all_memory();  // the block is in the slot (L2) before the next one reads it
+  }
+  if (lane == 0) ch.state[c] = state + ch.done_add;
 }
 
 }  // namespace
@@ -1177,7 +1272,8 @@ L4Two* l4_two() { return per_device<L4Two>(create_l4_two); }
 
 hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
-                              size_t ws_bytes, hipStream_t stream, hipStream_t pass1_stream) {
+                              size_t ws_bytes, hipStream_t stream, hipStream_t pass1_stream,
+                              const Lz4Chains* chains) {
   if (n_msgs == 0) return hipSuccess;
   const u64 fixed = kL4Head + 3 * l4_list_bytes(n_msgs);
   if (ws_bytes < fixed) return hipErrorInvalidValue;
@@ -1205,13 +1301,24 @@ hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len
   const u64 cap_words = lz4_decode_bitmap_capacity_words(n_msgs, ws_bytes);
   e = hipMemsetAsync(counter, 0, kL4Head, s1);
   if (e != hipSuccess) return e;
-  lz4_index_kernel<<<(n_msgs + 63) / 64, 64, 0, s1>>>(in, in_off, in_len, n_msgs, out_cap, out_len, status,
-                                                      counter, bm_base, hdr, bitmap, cap_words, big_list, big_min);
+  // (no chains: the forms without a prefix, the code the block calls always ran)
+  if (chains)
+    lz4_index_kernel<true><<<(n_msgs + 63) / 64, 64, 0, s1>>>(in, in_off, in_len, n_msgs, out_cap, out_len, status,
+                                                              counter, bm_base, hdr, bitmap, cap_words, big_list,
+                                                              big_min, chains->word, chains->shift);
+  else
+    lz4_index_kernel<false><<<(n_msgs + 63) / 64, 64, 0, s1>>>(in, in_off, in_len, n_msgs, out_cap, out_len, status,
+                                                               counter, bm_base, hdr, bitmap, cap_words, big_list,
+                                                               big_min, nullptr, 0);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   // (a grid of 256 blocks: with no listed block each wave reads the count and leaves)
-  lz4_index_big_kernel<<<256, kBigWaves * 64, 0, s1>>>(in, in_off, in_len, out_len, status, counter, big_list,
-                                                       bm_base, hdr, bitmap);
+  if (chains)
+    lz4_index_big_kernel<true><<<256, kBigWaves * 64, 0, s1>>>(in, in_off, in_len, out_len, status, counter, big_list,
+                                                               bm_base, hdr, bitmap, chains->word, chains->shift);
+  else
+    lz4_index_big_kernel<false><<<256, kBigWaves * 64, 0, s1>>>(in, in_off, in_len, out_len, status, counter, big_list,
+                                                                bm_base, hdr, bitmap, nullptr, 0);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (two) {
@@ -1219,10 +1326,21 @@ hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len
     if ((e = hipEventRecord(two->pass1, s1)) != hipSuccess) return e;
     if ((e = hipStreamWaitEvent(stream, two->pass1, 0)) != hipSuccess) return e;
   }
-  lz4_exec_kernel<<<(n_msgs + kL4Waves - 1) / kL4Waves, kL4Waves * 64, 0, stream>>>(
-      in, in_off, in_len, n_msgs, out, out_off, out_len, status, bm_base, hdr, bitmap);
+  if (chains)
+    lz4_exec_kernel<true><<<(n_msgs + kL4Waves - 1) / kL4Waves, kL4Waves * 64, 0, stream>>>(
+        in, in_off, in_len, n_msgs, out, out_off, out_len, status, bm_base, hdr, bitmap, chains->word,
+        chains->chained_mask);
+  else
+    lz4_exec_kernel<false><<<(n_msgs + kL4Waves - 1) / kL4Waves, kL4Waves * 64, 0, stream>>>(
+        in, in_off, in_len, n_msgs, out, out_off, out_len, status, bm_base, hdr, bitmap, nullptr, 0);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
+  if (chains && chains->n_chains) {
+    lz4_exec_chain_kernel<<<(chains->n_chains + kL4Waves - 1) / kL4Waves, kL4Waves * 64, 0, stream>>>(
+        in, in_off, in_len, n_msgs, out, out_off, out_len, status, bm_base, hdr, bitmap, *chains);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
   return launch_lz4_decode_fallback(in, in_off, in_len, n_msgs, out, out_off, out_cap, out_len, status,
                                     counter + kL4CtrFallback, stream);
 }

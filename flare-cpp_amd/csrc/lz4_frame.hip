@@ -7,7 +7,8 @@
 // lz4_decode2.hip) run a frame's blocks as if they were messages; the kernels
 // here only cut messages into blocks and put frames together (compress), or
 // take frames apart and judge the result (decompress).  Those launches are
-// called, not changed.
+// called as they are; launch_lz4_decode2 alone takes one more argument, for
+// the linked frames below.
 //
 // Compress: plan (a lane per message: its blocks' columns, staging slots from
 // two counters) -> launch_lz4_encode on the block columns -> XXH32 of the
@@ -28,6 +29,12 @@
 // the lengths) gives the blocks their places in the slot; stage, the block
 // decoder, verdict and finish go on as for the sized frames.
 // fsg_lz4f_decoded_lengths_batch is index, length and the sum alone.
+// With option lz4f_linked_fast, frames with linked blocks are listed the same
+// two ways, each entry with its prefix -- the bytes the frame produced before
+// the block, at most 65,535 -- and marked chained: the block decoder indexes
+// all of them side by side and one wave per frame executes the frame's blocks
+// in order (lz4_decode2.hip, lz4_exec_chain_kernel).  Finish accepts such a
+// frame only when its chain ran to the end.
 #include "launch.h"
 #include "lz4_frame_format.h"
 #include "lz4_frame_length.h"
@@ -53,16 +60,25 @@ constexpr u32 kFdStage = 10;    // u64
 constexpr u32 kFdNsMsgs = 12, kFdNsBlocks = 13;  // answered by the fast route without a content size
 constexpr u32 kFdBig = 14;      // length pass: blocks listed for the wave walk
 constexpr u32 kFdBigNext = 15;  // and the next of them to take
+constexpr u32 kFdLkMsgs = 16, kFdLkBlocks = 17;  // answered by the fast route for linked blocks
 constexpr u64 kHead = 256;
 
 // msg_route values
 constexpr u32 kRouteDone = 0, kRouteFast = 1, kRouteLinked = 2, kRouteNoSize = 3, kRouteRejected = 4,
               kRouteForced = 5;
 constexpr u32 kRouteNoSizeFast = 6;  // fast route without a content size (pending until finish accepts it)
+// linked blocks, pending: with a content size, without one (bit 0); the chain
+// wave that executed all of a frame's blocks adds kRouteChainDone
+constexpr u32 kRouteLinkedFast = 8, kRouteLinkedNsFast = 9, kRouteChainDone = 2;
+constexpr u32 kRouteLinkedOk = kRouteLinkedFast + kRouteChainDone, kRouteLinkedNsOk = kRouteLinkedNsFast + kRouteChainDone;
 // block flags
 constexpr u32 kBlkRaw = 1, kBlkSum = 2, kBlkFailed = 4, kBlkListed = 8;
 constexpr u32 kBlkUnknown = 16;  // decoded length unknown: the length pass finds it
+constexpr u32 kBlkChained = 32;  // a linked frame's block: executed by its frame's wave
 constexpr u32 kBlkMaxShift = 8;  // with kBlkUnknown: log2 of the frame's block maximum, from this bit up
+// a chained block's prefix, from this bit up (written by index, or by place
+// once the length pass, which reads f >> kBlkMaxShift, is over)
+constexpr u32 kBlkPrefixShift = 16;
 
 constexpr u32 kNoFit = 0xFFFFFFFFu;
 
@@ -285,9 +301,9 @@ __device__ inline bool walk_blocks(const u8* ib, u64 n, const lz4f::Header& h, b
 // out_off and out_cap stay 0 -- an empty body for the block decoder -- until
 // the place kernel knows the lengths.
 __device__ inline void list_unknown(const u8* ib, const lz4f::Header& h, u64 io, u32 nb, u32 base, u64 at,
-                                    BlockCols c) {
+                                    BlockCols c, u32 more_flags = 0) {
   const u32 bsum = (h.flg & lz4f::kFlgBlockSum) ? 4 : 0;
-  const u32 common = kBlkListed | kBlkUnknown | (bsum ? kBlkSum : 0) |
+  const u32 common = kBlkListed | kBlkUnknown | more_flags | (bsum ? kBlkSum : 0) |
                      ((u32)(31 - __builtin_clz(h.block_max)) << kBlkMaxShift);
   u64 ip = h.len;
   for (u32 k = 0; k < nb; ++k) {
@@ -314,7 +330,8 @@ __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ i
                                                       const u64* __restrict__ out_off, const u32* __restrict__ out_cap,
                                                       u32* __restrict__ out_len, i32* __restrict__ status, u32* hdr,
                                                       MsgCols mc, BlockCols c, u32 nb_cap, u64 stage_off,
-                                                      u64 stage_cap, u32 force_serial, u32 nosize_fast) {
+                                                      u64 stage_cap, u32 force_serial, u32 nosize_fast,
+                                                      u32 linked_fast) {
   const u32 m = blockIdx.x * 64 + threadIdx.x;
   if (m >= n_msgs) return;
   const u8* ib = in + in_off[m];
@@ -327,6 +344,13 @@ __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ i
     return;
   }
   const u64 cap = out_cap[m];
+  // linked blocks on the fast route: with a content size, or with both options
+  const bool linked = !(h.flg & lz4f::kFlgIndep);
+  const bool chain = linked && linked_fast && !force_serial && (h.size != lz4f::kNoSize || nosize_fast);
+  if (chain && h.size != lz4f::kNoSize && h.size > cap) {  // (the serial decoder answers from the descriptor)
+    mc.route[m] = kRouteRejected;
+    return;
+  }
   if (h.size != lz4f::kNoSize && h.size > cap) {
     out_len[m] = h.size > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)h.size;
     status[m] = kSlotTooSmall;
@@ -345,7 +369,7 @@ __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ i
     mc.route[m] = kRouteForced;
     return;
   }
-  if (!(h.flg & lz4f::kFlgIndep)) {
+  if (linked && !chain) {
     mc.route[m] = kRouteLinked;
     return;
   }
@@ -362,11 +386,11 @@ __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ i
     const u32 base = atomicAdd(&hdr[kFdBlocks], nb);
     const u64 sb = atomicAdd(reinterpret_cast<unsigned long long*>(hdr + kFdStage), (unsigned long long)need);
     if ((u64)base + nb > nb_cap || sb + need > stage_cap) return;
-    list_unknown(ib, h, in_off[m], nb, base, stage_off + sb, c);
+    list_unknown(ib, h, in_off[m], nb, base, stage_off + sb, c, chain ? kBlkChained : 0);
     mc.xxh[m] = xxh;
     mc.first[m] = base;
     mc.nb[m] = nb;
-    mc.route[m] = kRouteNoSizeFast;
+    mc.route[m] = chain ? kRouteLinkedNsFast : kRouteNoSizeFast;
     return;
   }
   // fast route: every block but the last is full
@@ -413,7 +437,8 @@ __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ i
     c.src_len[e] = sz;
     c.out_off[e] = oo + (u64)k * bs;
     c.out_cap[e] = exp;
-    c.flags[e] = kBlkListed | (raw ? kBlkRaw : 0) | (bsum ? kBlkSum : 0);
+    c.flags[e] = kBlkListed | (raw ? kBlkRaw : 0) | (bsum ? kBlkSum : 0) |
+                 (chain ? kBlkChained | (lz4f::linked_prefix((u64)k * bs) << kBlkPrefixShift) : 0);
     if (!raw) {
       c.in_off[e] = stage_off + sb;
       c.in_len[e] = (u32)varint32_len(exp) + sz;
@@ -423,7 +448,7 @@ __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ i
   }
   mc.first[m] = base;
   mc.nb[m] = nb;
-  mc.route[m] = kRouteFast;
+  mc.route[m] = chain ? kRouteLinkedFast : kRouteFast;
 }
 
 // ---- the length pass (frames without a content size)
@@ -488,7 +513,7 @@ __global__ __launch_bounds__(256) void lz4f_place_kernel(u32 n_msgs, const u64* 
                                                        u64* lengths, i32* status) {
   const u32 m = blockIdx.x * 4 + (threadIdx.x >> 6);
   const u32 lane = threadIdx.x & 63;
-  if (m >= n_msgs || mc.route[m] != kRouteNoSizeFast) return;
+  if (m >= n_msgs || (mc.route[m] != kRouteNoSizeFast && mc.route[m] != kRouteLinkedNsFast)) return;
   const u32 first = mc.first[m], nb = mc.nb[m];
   u64 total = 0;
   bool bad = false;
@@ -522,6 +547,10 @@ __global__ __launch_bounds__(256) void lz4f_place_kernel(u32 n_msgs, const u64* 
     if (valid) {
       c.out_off[e] = at + (incl - len);
       c.out_cap[e] = len;
+      // (flags without kBlkChained have no bits from kBlkPrefixShift up once the length pass is over)
+      if (c.flags[e] & kBlkChained)
+        c.flags[e] = (c.flags[e] & ((1u << kBlkPrefixShift) - 1)) |
+                     (lz4f::linked_prefix(at + (incl - len) - out_off[m]) << kBlkPrefixShift);
       if (!(c.flags[e] & kBlkRaw)) c.in_len[e] = (u32)varint32_len(len) + c.src_len[e];
     }
     at += __shfl(incl, 63, 64);
@@ -650,7 +679,10 @@ __global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ 
   const u8* ib = in + in_off[m];
   u8* ob = out + out_off[m];
   u32 blocks = 0, ns_blocks = 0, sums = 0;
-  if (route == kRouteFast) {
+  // a linked frame whose chain did not run to its end: the serial decoder
+  if (route == kRouteLinkedFast || route == kRouteLinkedNsFast) route = kRouteRejected;
+  const bool lk = route == kRouteLinkedOk || route == kRouteLinkedNsOk;
+  if (route == kRouteFast || route == kRouteLinkedOk) {
     const u32 first = mc.first[m], nb = mc.nb[m];
     bool ok = true;
     for (u32 k = 0; k < nb && ok; ++k) ok = !(c.flags[first + k] & kBlkFailed);
@@ -667,7 +699,7 @@ __global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ 
     } else {
       route = kRouteRejected;
     }
-  } else if (route == kRouteNoSizeFast) {
+  } else if (route == kRouteNoSizeFast || route == kRouteLinkedNsOk) {
     // the blocks lie end to end from the slot's start: decoded exactly the
     // lengths the walk found, and the checksum over them
     const u32 first = mc.first[m], nb = mc.nb[m], last = first + nb - 1;
@@ -688,7 +720,7 @@ __global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ 
       route = kRouteRejected;
     }
   }
-  if (route != kRouteFast && route != kRouteNoSizeFast) {
+  if (route != kRouteFast && route != kRouteNoSizeFast && !(lk && route != kRouteRejected)) {
     u32 ol, s = 0;
     status[m] = lz4f::decode_frame(ib, in_len[m], ob, out_cap[m], &ol, &s);
     out_len[m] = ol;
@@ -699,6 +731,11 @@ __global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ 
   count_lanes(&hdr[kFdNoSize], route == kRouteNoSize);
   count_lanes(&hdr[kFdRejected], route == kRouteRejected);
   count_lanes(&hdr[kFdForced], route == kRouteForced);
+  if (lk && route != kRouteRejected) {  // (no frame is on this route unless the option is set)
+    atomicAdd(&hdr[kFdLkMsgs], 1u);
+    atomicAdd(&hdr[kFdLkBlocks], blocks + ns_blocks);
+    blocks = ns_blocks = 0;
+  }
   if (blocks) atomicAdd(&hdr[kFdFastBlocks], blocks);
   if (sums) atomicAdd(&hdr[kFdSums], sums);
   if (ns_blocks) {  // (no frame is on this route unless the option is set)
@@ -825,8 +862,10 @@ void lz4f_encode_header_counts(const void* header, Lz4fEncodeHeaderCounts* c) {
   c->overflow_messages = ctr[kFcOverflow];
 }
 void lz4f_decode_header_counts(const void* header, Lz4fDecodeHeaderCounts* c) {
-  u32 ctr[14];
+  u32 ctr[kFdLkBlocks + 1];
   __builtin_memcpy(ctr, header, sizeof(ctr));
+  c->fast_linked_messages = ctr[kFdLkMsgs];
+  c->fast_linked_blocks = ctr[kFdLkBlocks];
   c->fast_nosize_messages = ctr[kFdNsMsgs];
   c->fast_nosize_blocks = ctr[kFdNsBlocks];
   c->fast_messages = ctr[kFdFastMsgs];
@@ -930,8 +969,8 @@ hipError_t launch_lz4f_decoded_lengths(const u8* in, const u64* in_off, const u3
 
 hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
-                              size_t ws_bytes, bool force_serial, bool nosize_fast, u32 length_wave_min,
-                              hipStream_t stream) {
+                              size_t ws_bytes, bool force_serial, bool nosize_fast, bool linked_fast,
+                              u32 length_wave_min, hipStream_t stream) {
   if (n_msgs == 0) return hipSuccess;
   Plan p;
   if (!plan_for(ws_bytes, &p, [&](u64 t, Plan* q) { return dec_plan(n_msgs, t, q); })) return hipErrorInvalidValue;
@@ -945,7 +984,8 @@ hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len
   if (e != hipSuccess) return e;
   lz4f_index_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out_off, out_cap, out_len,
                                                           status, hdr, mc, c, p.nb_cap, p.off_stage, p.stage_cap,
-                                                          force_serial ? 1u : 0u, nosize_fast ? 1u : 0u);
+                                                          force_serial ? 1u : 0u, nosize_fast ? 1u : 0u,
+                                                          linked_fast ? 1u : 0u);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const u32* inner_fallback = nullptr;
   if (!force_serial && nosize_fast) {
@@ -957,8 +997,12 @@ hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len
     const u32 grid = (p.nb_cap + 3) / 4 < 8192 ? (p.nb_cap + 3) / 4 : 8192;
     lz4f_stage_kernel<<<grid, 256, 0, stream>>>(in, out, w, c, p.nb_cap);
     if ((e = hipGetLastError()) != hipSuccess) return e;
+    // option lz4f_linked_fast: the flags column carries the prefixes, the
+    // route column the chains' results; without it, the launch of before
+    const Lz4Chains chains{c.flags,  kBlkPrefixShift, kBlkChained,      kBlkRaw,          n_msgs, mc.first,
+                           mc.nb,    mc.route,        kRouteLinkedFast, 1u,               kRouteChainDone};
     e = launch_lz4_decode2(w, c.in_off, c.in_len, p.nb_cap, out, c.out_off, c.out_cap, c.out_len, c.status,
-                           w + p.off_inner, p.inner_bytes, stream, nullptr);
+                           w + p.off_inner, p.inner_bytes, stream, nullptr, linked_fast ? &chains : nullptr);
     if (e != hipSuccess) return e;
     lz4f_verdict_kernel<<<(p.nb_cap + 63) / 64, 64, 0, stream>>>(in, c, p.nb_cap, hdr);
     if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -224,6 +224,10 @@ LZ4F_HD bool block_decode(const uint8_t* src, uint32_t n, uint8_t* dst, uint32_t
   }
 }
 
+// The history a linked block can reach: the bytes its frame produced before
+// it, as far as an offset goes.
+LZ4F_HD uint32_t linked_prefix(uint64_t produced) { return produced < 65535 ? (uint32_t)produced : 65535u; }
+
 // ---- the serial frame decoder: one frame per body, every write below
 // out + cap.  *out_len: the decoded length on kStOk, min(content size, 2^32-1)
 // on kStSlotTooSmall, else 0.  *checksums (may be null): block and content

@@ -44,6 +44,7 @@ enum Opt : int {
   kOptLz4fBlockWaveMin,   // the block encode's wave threshold (as lz4_encode_wave_min; -1: its automatic rule)
   kOptLz4fNosizeFast,     // 1: frames with independent blocks and no content size on the block decoders
   kOptLz4fLengthWaveMin,  // -1 automatic; blocks above this many bytes get their length by a wave (>= 0xFFFFFFFF: none)
+  kOptLz4fLinkedFast,     // 1: frames with linked blocks on the block decoders, a wave per frame executing in order
   kOptCount
 };
 

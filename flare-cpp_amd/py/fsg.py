@@ -47,7 +47,7 @@ Lz4fEncodeReport = _report_struct("Lz4fEncodeReport", (
 Lz4fDecodeReport = _report_struct("Lz4fDecodeReport", (
     "fast_messages", "fast_blocks", "empty_messages", "serial_linked", "serial_no_size", "serial_rejected",
     "serial_forced", "checksummed_units", "inner_fallback_blocks", "block_entries", "fast_nosize_messages",
-    "fast_nosize_blocks"))
+    "fast_nosize_blocks", "fast_linked_messages", "fast_linked_blocks"))
 LZ4F_NO_CONTENT_SIZE = 0xFFFFFFFFFFFFFFFF
 PATH_MAIN, PATH_SINGLE_DESIGN, PATH_NO_WORKSPACE, PATH_FORCED = 0, 1, 2, 3
 

@@ -213,7 +213,25 @@ int fsg_lz4_compress_report(const void *header_host_copy, uint32_t n_msgs,
  * A frame that fails the structure check, does not fit the workspace, has a
  * block without a length, decodes to more than d_out_cap[i], or has a block or
  * a checksum that fails goes to the serial decoder, so the route never changes
- * a byte or a status.  Linked frames stay serial.
+ * a byte or a status.
+ *
+ * With option lz4f_linked_fast (FSG_L4F_LINKED_FAST) = 1 (default 0) a frame
+ * with linked blocks takes a fast route too: one with a content size within
+ * the capacity is listed as a sized frame with independent blocks is, one
+ * without a content size as the paragraph above lists its frames, and that
+ * only when lz4f_nosize_fast is 1 as well (otherwise it stays on the serial
+ * decoder).  Each block also gets its prefix, the bytes the frame produced
+ * before it, at most 65,535: the index passes of the block decoder, which run
+ * on all blocks of the batch side by side, accept offsets that stay inside
+ * it, and one wave per frame executes the frame's blocks in order, so every
+ * history byte it reads is one it stored before or a raw block put in place
+ * by an earlier launch.  The wave stops at the first block that failed or
+ * whose bitmap did not fit the workspace; a frame whose wave did not finish
+ * all its blocks, and every frame with a block or checksum that fails, goes
+ * to the serial decoder (serial_rejected), as does a linked frame whose
+ * content size is above the capacity, so this route never changes a byte or a
+ * status either.  Frames it answers are counted in fast_linked_messages, not
+ * in fast_messages, fast_nosize_messages or serial_linked.
  *
  * "What a *_batch call writes" holds for both calls, every status and route.
  * Slots: fsg_lz4f_max_frame_length(d_in_len[i], id) for compress. */
@@ -258,7 +276,7 @@ size_t fsg_lz4f_decompress_workspace_bytes(uint32_t n_msgs, uint64_t total_in_by
 
 /* Batched frame decompress, columns as fsg_lz4_decompress_batch_ws.  Option
  * lz4f_force_serial (FSG_L4F_FORCE_SERIAL) = 1 sends every frame to the serial
- * decoder; lz4f_nosize_fast and lz4f_length_wave_min: "Routes" above.  A NULL workspace or one below
+ * decoder; lz4f_nosize_fast, lz4f_length_wave_min and lz4f_linked_fast: "Routes" above.  A NULL workspace or one below
  * fsg_lz4f_decompress_workspace_bytes(n_msgs, 0) is FSG_ERR_INVALID_ARG;
  * n_msgs == 0 succeeds and launches nothing. */
 int fsg_lz4f_decompress_batch(const uint8_t *d_in, const uint64_t *d_in_off,
@@ -320,7 +338,7 @@ struct fsg_lz4f_decode_report {
   uint64_t fast_messages;      /* answered by the fast route (FSG_OK) */
   uint64_t fast_blocks;        /* their blocks */
   uint64_t empty_messages;     /* frames without blocks, finished by the index pass */
-  uint64_t serial_linked;      /* serial route: linked blocks */
+  uint64_t serial_linked;      /* serial route: linked blocks (option lz4f_linked_fast 0, or no content size and lz4f_nosize_fast 0) */
   uint64_t serial_no_size;     /* serial route: no content size (option lz4f_nosize_fast 0) */
   uint64_t serial_rejected;    /* serial route: a fast route, with or without a content size, did not accept the frame */
   uint64_t serial_forced;      /* serial route: option lz4f_force_serial */
@@ -329,6 +347,8 @@ struct fsg_lz4f_decode_report {
   uint64_t block_entries;      /* blocks the workspace holds */
   uint64_t fast_nosize_messages; /* answered by the fast route for frames without a content size (FSG_OK) */
   uint64_t fast_nosize_blocks;   /* their blocks */
+  uint64_t fast_linked_messages; /* answered by the fast route for linked blocks (FSG_OK) */
+  uint64_t fast_linked_blocks;   /* their blocks */
 };
 int fsg_lz4f_decompress_report(const void *header_host_copy, uint32_t n_msgs,
                                size_t workspace_bytes,

@@ -8,6 +8,7 @@ per call.  One JSON line per row.
     python tools/lz4f_bench.py [--rows 16x4m,c3] [--launches 7] [--warmup 2] [--bid 4]
     python tools/lz4f_bench.py --no-size [--rows 16x4m@7,16x4m@7c,c3,1x64k] [--bid 4] [--checksum 1]
     python tools/lz4f_bench.py --length-pass
+    python tools/lz4f_bench.py --linked [--rows 16x4m@4,16x4m@7,4096x128k@4,1x128k@4] [--sys-linked 1]
 
 Rows: 16x4m (16 x 4 MiB: 64 independent blocks a body, where the format adds
 parallelism) and c3 (65,536 x 64 KiB: one block a body, the cost of the plan,
@@ -22,6 +23,16 @@ decoder) and at 1 (the block decoders), alternating; a library without the
 option gives the serial figure alone.  --length-pass: the length pass by
 itself (fsg_lz4f_decoded_lengths_batch on one-block frames without a content
 size), one lane per block against one wave per block, by block size and batch.
+
+--linked: the rows' frames with B.Indep cleared in FLG and HC recomputed on
+the host -- valid linked frames with the same bytes, which take the routes of
+linked frames but hold no copy that reaches into an earlier block -- each with
+and without a content size, through fsg_lz4f_decompress_batch with options
+lz4f_linked_fast and lz4f_nosize_fast both 0 (the serial decoder) and both 1
+(a wave per frame), alternating; a library without the option gives the
+serial figure alone.  --sys-linked 1: one more row, 16 x 4 MiB at id 4 written
+by the system liblz4 with LZ4F_blockLinked (copies into history included);
+reported as missing where liblz4 is not installed.
 """
 import argparse
 import json
@@ -35,7 +46,8 @@ for p in (REPO / "flare-cpp_amd" / "py", REPO / "oracle", REPO / "tests"):
     sys.path.insert(0, str(p))
 import fsg  # noqa: E402
 
-ROWS = {"16x4m": (16, 4 << 20), "c3": (65536, 64 << 10), "256x256k": (256, 256 << 10), "1x64k": (1, 64 << 10)}
+ROWS = {"16x4m": (16, 4 << 20), "c3": (65536, 64 << 10), "256x256k": (256, 256 << 10), "1x64k": (1, 64 << 10),
+        "4096x128k": (4096, 128 << 10), "1x128k": (1, 128 << 10)}
 NONE = 0xFFFFFFFF
 
 
@@ -226,6 +238,121 @@ def nosize_row(torch, codec, name, bid, checksum, warmup, launches):
     print(json.dumps(out), flush=True)
 
 
+def linked_frames(torch, codec, batch, bid, sized):
+    """(bytes, offsets, lengths as host arrays) of the batch's frames as linked
+    frames: compressed on the device, B.Indep cleared and the descriptor's
+    check byte made right on the host; without the content size field unless
+    `sized`."""
+    import lz4f_ref
+    dev = torch.device("cuda", 0)
+    lib = codec.lib
+    n = len(batch)
+    H = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    f_off, f_tot = fsg.slot_offsets(np.array([lib.fsg_lz4f_max_frame_length(int(x), bid) for x in batch.lens], np.uint64))
+    d_f = torch.zeros(f_tot, dtype=torch.uint8, device=dev)
+    d_fl = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+    ws = codec.lz4f_compress_workspace(n, batch.total, bid)
+    codec.lz4f_compress(H(batch.data), H(batch.offsets), H(batch.lens), n, d_f, H(f_off), d_fl, d_st, ws,
+                        block_size_id=bid, checksum=False)
+    torch.cuda.synchronize()
+    assert int((d_st != 0).sum().item()) == 0
+    host = d_f.cpu().numpy()
+    flen = d_fl.cpu().numpy().view(np.uint32).astype(np.uint64)
+    cut = 0 if sized else 8
+    lens = (flen - cut).astype(np.uint32)
+    offs, total = fsg.slot_offsets(lens.astype(np.uint64))
+    out = np.zeros(total, np.uint8)
+    for i in range(n):
+        a, b = int(f_off[i]), int(offs[i])
+        head = bytes(host[a:a + 14])
+        assert head[4] & lz4f_ref.F_SIZE and head[4] & lz4f_ref.F_INDEP
+        flg = head[4] & ~lz4f_ref.F_INDEP & (0xFF if sized else ~lz4f_ref.F_SIZE)
+        d = bytes([flg, head[5]]) + (head[6:14] if sized else b"")
+        hl = 7 + len(d) - 2
+        out[b:b + 4] = host[a:a + 4]
+        out[b + 4:b + hl] = np.frombuffer(d + bytes([(lz4f_ref.xxh32(d) >> 8) & 0xFF]), np.uint8)
+        out[b + hl:b + int(lens[i])] = host[a + 15:a + int(flen[i])]
+    return out, offs, lens
+
+
+def sys_linked_frames(batch, bid):
+    """The batch's frames written by the system liblz4 with linked blocks and a
+    content size, or None where it is not installed."""
+    import lz4f_sys
+    L = lz4f_sys.load()
+    if L is None:
+        return None
+    z = lz4f_sys.SysLz4F(L)
+    frames = [z.compress_frame(batch.item(i), bid, mode=lz4f_sys.LINKED) for i in range(len(batch))]
+    lens = np.array([len(f) for f in frames], np.uint32)
+    offs, total = fsg.slot_offsets(lens.astype(np.uint64))
+    out = np.zeros(total, np.uint8)
+    for f, at in zip(frames, offs):
+        out[int(at):int(at) + len(f)] = np.frombuffer(f, np.uint8)
+    return out, offs, lens
+
+
+def linked_row(torch, codec, name, bid, sized, warmup, launches, from_sys=False):
+    dev = torch.device("cuda", 0)
+    n, size = ROWS[name]
+    batch = fsg.make_batch(fsg.KIND_TEXT, np.full(n, size, np.uint32))
+    H = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    s = torch.cuda.current_stream()
+    routed = has_option("lz4f_linked_fast")
+    out = {"mode": "linked", "row": name, "n": n, "size": size, "block_size_id": bid, "sized": int(sized),
+           "frames": "liblz4" if from_sys else "device", "launches": launches, "warmup": warmup,
+           "raw_bytes": batch.total, "has_option": routed}
+    made = sys_linked_frames(batch, bid) if from_sys else linked_frames(torch, codec, batch, bid, sized)
+    if made is None:
+        out["missing"] = "no system liblz4"
+        print(json.dumps(out), flush=True)
+        return
+    data, offs, lens = made
+    torch.cuda.empty_cache()
+    out["frame_bytes"] = int(lens.sum())
+    d_f, d_fo, d_fl = H(data), H(offs), H(lens)
+    d_raw, d_ro, d_rl = H(batch.data), H(batch.offsets), H(batch.lens)
+    d_out = torch.full((batch.total,), 0xA5, dtype=torch.uint8, device=dev)
+    d_ol = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+    ws = codec.lz4f_decompress_workspace(n, int(data.size))
+    names = ("lz4f_linked_fast", "lz4f_nosize_fast")
+
+    def call(fast):
+        def fn():
+            if routed:
+                for k in names:
+                    fsg.set_option(k, fast)
+            codec.lz4f_decompress(d_f, d_fo, d_fl, n, d_out, d_ro, d_rl, d_ol, d_st, ws, stream=s)
+        return fn
+
+    def check():
+        return int((d_st != 0).sum().item()) == 0 and bool(torch.equal(d_out, d_raw))
+
+    if routed:
+        saved = [fsg.get_option(k) for k in names]
+        ms = alternate(torch, s, (call(0), call(1)), warmup, launches)
+        out["serial_call"], out["fast_call"] = ms
+        out["gain"] = round(ms[0]["median_ms"] / ms[1]["median_ms"], 3)
+        d_out.fill_(0xA5)
+        call(1)()
+        torch.cuda.synchronize()
+        out["fast_ok"] = check()
+        out["fast_report"] = codec.lz4f_decompress_report(ws, n)
+        d_out.fill_(0xA5)
+        call(0)()
+        torch.cuda.synchronize()
+        out["serial_ok"] = check()
+        for k, v in zip(names, saved):
+            fsg.set_option(k, v)
+    else:
+        out["serial_call"] = alternate(torch, s, (call(0),), warmup, launches)[0]
+        out["serial_ok"] = check()
+    out["serial_report"] = codec.lz4f_decompress_report(ws, n)
+    print(json.dumps(out), flush=True)
+
+
 def length_pass(torch, codec, warmup, launches, limit_bytes=2 << 30):
     """Lane against wave for the length pass alone."""
     dev = torch.device("cuda", 0)
@@ -267,6 +394,8 @@ def main():
     ap.add_argument("--no-size", action="store_true", help="frames without a content size: serial against routed")
     ap.add_argument("--checksum", type=int, default=0, help="--no-size: frames with a content checksum")
     ap.add_argument("--length-pass", action="store_true", help="the length pass alone: lane against wave")
+    ap.add_argument("--linked", action="store_true", help="linked frames, sized and not: serial against a wave per frame")
+    ap.add_argument("--sys-linked", type=int, default=0, help="--linked: also 16x4m at id 4 written by the system liblz4")
     ap.add_argument("--bid", type=int, default=4, help="block size id 4..7")
     ap.add_argument("--launches", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
@@ -277,6 +406,16 @@ def main():
     codec = fsg.SnappyGPU(0)
     if a.length_pass:
         length_pass(torch, codec, a.warmup, a.launches)
+        return
+    if a.linked:
+        rows = "16x4m@4,16x4m@7,4096x128k@4,1x128k@4" if a.rows == "16x4m,c3" else a.rows
+        for item in rows.split(","):
+            name, _, spec = item.partition("@")
+            for sized in (True, False):
+                linked_row(torch, codec, name, int(spec) if spec else a.bid, sized, a.warmup, a.launches)
+                torch.cuda.empty_cache()
+        if a.sys_linked:
+            linked_row(torch, codec, "16x4m", 4, True, a.warmup, a.launches, from_sys=True)
         return
     for name in a.rows.split(","):
         if a.no_size:  # row[@id[c]]: a block size id and a content checksum of the row's own
