@@ -314,7 +314,12 @@ __attribute__((amdgpu_waves_per_eu(kLean ? 6 : 1))) void index_kernel(
     status = -1;
   }
   const bool walked = status < 0;  // (planned: the other lanes' statuses stand)
-  u32* bm = bitmap ? bitmap + bm_base : nullptr;
+  // Planned without a walk order (option walk_order 0) the lanes cover every
+  // message, also those the plan gave a final status or listed for pass 1b:
+  // such a lane keeps kOk and bitmap base 0 here and has its input length, so
+  // with a bitmap pointer it would store ceil(n_in / 128) zero groups over
+  // the words of whichever messages were allocated first.  No pointer for it.
+  u32* bm = bitmap && (!kPlanned || walked) ? bitmap + bm_base : nullptr;
 
   const u32 ibal = (u32)(reinterpret_cast<uintptr_t>(ib) & 15);
   const u8* abase = ib - ibal;

@@ -265,7 +265,11 @@ __device__ __forceinline__ void exec5_packed(
       continue;
     }
     const u32 avail = tail - head;
-    if (avail == 0) break;
+    // (op >= op_end, as exec5_message's op >= op1: the last body's output is
+    // complete; what pass 1 accepted after it are zero-length literals, which
+    // no group would take -- t_op < op_end below -- so the loop would spin to
+    // its guard and hand the whole batch to pass 3)
+    if (avail == 0 || op >= op_end) break;
     const u32 take0 = avail < 64 ? avail : 64u;
     const bool valid = lane < take0;
     const u32 ent = ring[(head + lane) & (kTagRing - 1)];

@@ -149,7 +149,14 @@ int fsg_set_split_region_cap(uint32_t bytes);
  *   chunked_huge, small_persist, small_batch, split_huge, walk_order,
  *   lean_walk, exec_big_blocks, exec_prio, exec_big_blocks_fork, exec_pack,
  *   encode_wave_min, encode_wave_share, encode_wave_all_mb,
- *   encode_lanes, encode_wave_per_cu, encode_wave_wg, lz4_big_min.
+ *   encode_lanes, encode_wave_per_cu, encode_wave_wg, lz4_big_min,
+ *   and the LZ4 side's, described in flare_lz4_gpu.h: lz4_encode_wave_min,
+ *   lz4_encode_wave_per_cu, lz4f_force_serial, lz4f_block_wave_min,
+ *   lz4f_nosize_fast, lz4f_length_wave_min, lz4f_linked_fast.
+ * The launch range-checks what it reads (decode: csrc/decode_v4_plan.h):
+ * split_class is taken modulo 16 (size class c = bodies under 2^(16 - c)
+ * compressed bytes), exec_pack outside 1..64 means 0, block counts outside
+ * 1..2^20 and an exec_keep outside its range mean the default.
  * Every value produces the same bytes and statuses.  Set between batches, not
  * while other threads launch.  FSG_ERR_INVALID_ARG for an unknown name.
  * fsg_default_option returns the built-in default (before the environment). */

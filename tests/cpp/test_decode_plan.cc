@@ -234,6 +234,21 @@ static void test_options() {
   CHECK(d.split_mode == 3 && d.split_class == 4 && d.split_huge && d.walk_order && d.prio == 1 &&
             d.big_blocks == 250 && d.fork_big_blocks == 250 && d.small_blocks == 250,
         "default options");
+  // split_class: every value is a size class 0..15 (modulo 16, of the value
+  // as u32), so every one names an existing walk_hist offset
+  for (i64 c : {(i64)0, (i64)1, (i64)7, (i64)8, (i64)15, (i64)16, (i64)255, (i64)256, (i64)-1, (i64)1 << 40}) {
+    DecodeOpts s;
+    s.split_class = c;
+    const u32 got = decode_v4_plan(1000, ws, false, s).split_class;
+    CHECK(got == (u32)c % kWalkClasses && got < kWalkClasses, "split_class %lld: %u", (long long)c, got);
+  }
+  // exec_prio and the flags: any non-zero value is "on"
+  for (i64 v : {(i64)-1, (i64)2, (i64)1 << 40}) {
+    DecodeOpts s;
+    s.exec_prio = s.split_huge = s.walk_order = s.chunked_huge = v;
+    const DecodePlan sp = decode_v4_plan(1000, ws, false, s);
+    CHECK(sp.prio == 1 && sp.split_huge && sp.walk_order && sp.chunked == d.chunked, "flag %lld", (long long)v);
+  }
   o.exec_big_blocks = 0;  // out of range: the defaults
   o.exec_big_blocks_fork = (1 << 20) + 1;
   const size_t ws2 = decode_v4_workspace_bytes(1u << 20, 0);

@@ -90,6 +90,9 @@ class GpuCodec:
         self.use_workspace = use_workspace
         self.torch = torch
         self.codec = fsg.SnappyGPU(torch.cuda.current_device())
+        # the path report of the last compress / decompress call
+        # (fsg_compress_report / fsg_decompress_report), as a dict
+        self.last_report = None
 
     def compress(self, batch: fsg.Batch):
         torch = self.torch
@@ -106,6 +109,7 @@ class GpuCodec:
         self.codec.compress(ins["d_in"], ins["d_in_off"], ins["d_in_len"], n, mx, d_out, ins["d_out_off"], d_ol, d_st,
                             workspace=ws)
         torch.cuda.synchronize()
+        self.last_report = self.codec.compress_report(ws, n, mx)
         out = d_out.cpu().numpy()
         check_call(out, lay, caps, {"d_out_len": d_ol, "d_status": d_st}, n, whole, ins)
         ol = d_ol.cpu().numpy()[:n].view(np.uint32)
@@ -140,6 +144,7 @@ class GpuCodec:
         self.codec.decompress(ins["d_in"], ins["d_in_off"], ins["d_in_len"], n, d_out, ins["d_out_off"],
                               ins["d_out_cap"], d_ol, d_st, flags=flags, workspace=ws)
         torch.cuda.synchronize()
+        self.last_report = self.codec.decompress_report(ws, n, flags)
         out = d_out.cpu().numpy()
         check_call(out, lay, caps, {"d_out_len": d_ol, "d_status": d_st}, n, whole, ins)
         if flags & fsg.FSG_FLAG_VALIDATE_ONLY:

@@ -3,6 +3,7 @@ include/flare_snappy_gpu.h declares, and its host-side helpers agree with the
 oracle (no compute calls are made without a GPU)."""
 import ctypes
 import json
+import re
 from pathlib import Path
 
 import pytest
@@ -72,7 +73,17 @@ def test_option_calls():
              "small_batch", "split_huge", "walk_order", "lean_walk", "exec_big_blocks", "exec_prio",
              "exec_big_blocks_fork", "exec_pack", "encode_wave_min", "encode_wave_share",
              "encode_wave_all_mb", "encode_lanes", "encode_wave_per_cu", "encode_wave_wg",
-             "lz4_big_min"]
+             "lz4_big_min", "lz4_encode_wave_min", "lz4_encode_wave_per_cu", "lz4f_force_serial",
+             "lz4f_block_wave_min", "lz4f_nosize_fast", "lz4f_length_wave_min", "lz4f_linked_fast"]
+    # every row of the option table (capi.hip kOptDesc: {"name", "FSG_ENV", default}), in its order
+    capi = (Path(__file__).resolve().parents[1] / "flare-cpp_amd" / "csrc" / "capi.hip").read_text()
+    table = re.findall(r'^\s*\{"([a-z0-9_]+)",\s*"FSG_[A-Z0-9_]+",\s*-?\d+\},', capi, flags=re.M)
+    assert table == names
+    # ... and the header's list (include/flare_snappy_gpu.h, above fsg_set_option) names each
+    header = fsg.HEADER.read_text()
+    doc = header[header.index("Process-wide tuning and test options"):header.index("int fsg_set_option(")]
+    listed = set(re.findall(r"[a-z][a-z0-9_]+", doc))
+    assert not [n for n in names if n not in listed]
     v = ctypes.c_int64(0)
     for n in names:
         assert lib.fsg_default_option(n.encode(), ctypes.byref(v)) == 0, n

@@ -10,7 +10,8 @@ import pytest
 import fsg
 from bind import Oracle
 from gen_inputs import build_input
-from snappy_streams import copy_tag as _copy, lit_tag as _lit, synthetic_stream as _synthetic_stream
+from snappy_batches import small_bodies_forked_batch
+from snappy_streams import synthetic_stream as _synthetic_stream
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 pytestmark = pytest.mark.gpu
@@ -311,35 +312,7 @@ def test_small_bodies_forked(gpu, oracle, pack, skew, fsg_opts):
     of the packed execution pass (exec_pack; 0 = a wave per body); skew:
     output slots of every alignment (gpu_harness slot_skew)."""
     fsg_opts(decode_fork=1, exec_pack=pack)
-    rng = np.random.default_rng(77)
-    comps = []
-    for n in list(range(1, 200, 7)) + list(range(200, 800, 23)):
-        comps.append(oracle.compress(fsg.make_batch(fsg.KIND_TEXT, [n], first_index=n).item(0)))
-    for i in range(400):
-        c, _ = _synthetic_stream(rng, int(rng.integers(1, 760)))
-        comps.append(c)
-    for n in (1, 15, 16, 17, 63, 64, 65, 100, 300, 490):
-        comps.append(oracle.compress(rng.integers(0, 256, n, dtype=np.uint8).tobytes()))
-    for n in (700, 768, 769, 2000, 5000, 20000):  # runs: small compressed, large output
-        comps.append(oracle.compress(bytes([n % 251]) * n))
-    comps.append(b"\x05" + _lit(b"abcde"))                          # 1-byte literal length field
-    comps.append(b"\x46" + b"\xf0\x45" + bytes(range(70)))           # literal of 70 bytes, nb = 1
-    comps.append(b"\x46" + b"\xfc\x45\x00\x00\x00" + bytes(range(70)))  # nb = 4
-    comps.append(b"\x0a" + _lit(b"ab") + _copy(2, 8, wide=True))
-    base = list(comps)
-    for _ in range(600):
-        c = bytearray(base[int(rng.integers(len(base)))])
-        for _ in range(int(rng.integers(1, 3))):
-            c[int(rng.integers(len(c)))] = int(rng.integers(256))
-        if rng.random() < 0.2:
-            c = c[: int(rng.integers(1, len(c) + 1))]
-        comps.append(bytes(c))
-    comps += [c + b"\xfc\xff\xff\xff\xff" for c in base[:40]]
-    comps += [bytes.fromhex(v["hex"]) for v in json.loads((GOLDEN / "negative.json").read_text())
-              if v["header_ok"] and v["ulen"] <= 1 << 16]
-    # padded with larger text bodies so the batch has every path of the fork
-    comps += [oracle.compress(fsg.make_batch(fsg.KIND_TEXT, [n], first_index=n).item(0))
-              for n in (3000, 9000, 70000)]
+    comps = small_bodies_forked_batch(oracle)
     assert sum(len(c) < 512 for c in comps) > 1000
     caps = [1 << 17] * len(comps)
     outs, ol, st = gpu.decompress(comps, caps, slot_skew=skew)
