@@ -593,16 +593,31 @@ size_t fsg_lz4f_max_frame_length(size_t n, uint32_t block_size_id) {
   return 15 + 4 * ((n + bs - 1) / bs) + n + 4 + 4;
 }
 
+size_t fsg_lz4f_max_frame_length_flags(size_t n, uint32_t block_size_id, uint32_t flags) {
+  if (block_size_id < 4 || block_size_id > 7 || flags > 7) return 0;
+  const size_t bs = (size_t)1 << (8 + 2 * block_size_id);
+  return fsg_lz4f_max_frame_length(n, block_size_id) + ((flags & FSG_LZ4F_FLAG_BLOCK_CHECKSUMS) ? 4 * ((n + bs - 1) / bs) : 0);
+}
+
+int fsg_lz4f_xxh32_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_msgs,
+                         uint32_t seed, uint32_t* d_xxh, void* stream) {
+  if (n_msgs == 0) return FSG_SUCCESS;
+  if (!d_in || !d_in_off || !d_in_len || !d_xxh) return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_lz4f_xxh32(d_in, d_in_off, d_in_len, n_msgs, seed, d_xxh, (hipStream_t)stream),
+                "fsg_lz4f_xxh32_batch");
+}
+
 size_t fsg_lz4f_compress_workspace_bytes(uint32_t n_msgs, uint64_t total_in_bytes, uint32_t block_size_id) {
   if (block_size_id < 4 || block_size_id > 7) return 0;
   return fsg::lz4f_compress_workspace_bytes(n_msgs, total_in_bytes, block_size_id);
 }
 
-int fsg_lz4f_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
-                            uint32_t n_msgs, uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len,
-                            int32_t* d_status, uint32_t block_size_id, uint32_t flags, void* d_workspace,
-                            size_t workspace_bytes, void* stream) {
-  if (block_size_id < 4 || block_size_id > 7 || (flags & ~1u)) return FSG_ERR_INVALID_ARG;
+int fsg_lz4f_compress_batch_flags(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                  uint32_t n_msgs, uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len,
+                                  int32_t* d_status, uint32_t block_size_id, uint32_t flags, void* d_workspace,
+                                  size_t workspace_bytes, void* stream) {
+  const uint32_t known = FSG_LZ4F_FLAG_CONTENT_CHECKSUM | FSG_LZ4F_FLAG_BLOCK_CHECKSUMS | FSG_LZ4F_FLAG_NO_CONTENT_SIZE;
+  if (block_size_id < 4 || block_size_id > 7 || (flags & ~known)) return FSG_ERR_INVALID_ARG;
   if (n_msgs == 0) return FSG_SUCCESS;
   if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len || !d_status || !d_workspace)
     return FSG_ERR_INVALID_ARG;
@@ -612,6 +627,16 @@ int fsg_lz4f_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off, const
                                         block_size_id, flags, d_workspace, workspace_bytes,
                                         lz4f_block_wave_min(entries), (hipStream_t)stream),
                 "fsg_lz4f_compress_batch");
+}
+
+// the call from before the flags word had bits 1 and 2: it keeps rejecting them
+int fsg_lz4f_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                            uint32_t n_msgs, uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len,
+                            int32_t* d_status, uint32_t block_size_id, uint32_t flags, void* d_workspace,
+                            size_t workspace_bytes, void* stream) {
+  if (flags & ~FSG_LZ4F_FLAG_CONTENT_CHECKSUM) return FSG_ERR_INVALID_ARG;
+  return fsg_lz4f_compress_batch_flags(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_len, d_status,
+                                       block_size_id, flags, d_workspace, workspace_bytes, stream);
 }
 
 size_t fsg_lz4f_decompress_workspace_bytes(uint32_t n_msgs, uint64_t total_in_bytes) {

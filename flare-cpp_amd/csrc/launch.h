@@ -108,6 +108,9 @@ u32 lz4f_decompress_block_capacity(u32 n_msgs, size_t ws_bytes);
 hipError_t launch_lz4f_encode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, u32* out_len, i32* status, u32 block_size_id, u32 flags, void* ws,
                               size_t ws_bytes, u64 wave_min, hipStream_t stream);
+// fsg_lz4f_xxh32_batch: XXH32 of each body on the checksum kernel (lz4f_xxh.h), no workspace
+hipError_t launch_lz4f_xxh32(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u32 seed, u32* xxh,
+                             hipStream_t stream);
 hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
                               size_t ws_bytes, bool force_serial, bool nosize_fast, bool linked_fast,

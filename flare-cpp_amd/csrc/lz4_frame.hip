@@ -12,16 +12,19 @@
 //
 // Compress: plan (a lane per message: its blocks' columns, staging slots from
 // two counters) -> launch_lz4_encode on the block columns -> XXH32 of the
-// inputs when a content checksum is asked for -> assemble (a wave per message:
-// prefix sum of the stored sizes, size words, block copies, descriptor, end
-// mark).
+// inputs when a content checksum is asked for, and of every block's bytes as
+// stored when block checksums are (the checksum kernel, lz4f_xxh.h: a quad of
+// lanes per unit) -> assemble (a wave per message: prefix sum of the stored
+// sizes, size words, block copies, block checksums, descriptor, end mark).
 // Decompress: index (a lane per message: descriptor, route, the walk over the
 // block size words, block columns) -> stage (a wave per block: varint32 +
 // block bytes into the workspace, a raw block straight to its place) ->
-// launch_lz4_decode2 on the block columns -> verdict (a lane per block: block
-// checksum, status, length) -> finish (a lane per message: content checksum,
-// status; and the serial decoder, lz4_frame_format.h, for linked blocks,
-// frames without a content size and every frame the fast route did not accept).
+// launch_lz4_decode2 on the block columns -> the checksum kernel on the listed
+// blocks that carry a checksum -> verdict (a lane per block: status, length)
+// -> the checksum kernel on the output of every pending frame with a content
+// checksum -> finish (a lane per message: status; and the serial decoder,
+// lz4_frame_format.h, for linked blocks, frames without a content size and
+// every frame the fast route did not accept).
 // With option lz4f_nosize_fast, frames with independent blocks and no content
 // size go block-parallel too: index lists their blocks with the length unknown,
 // length (a lane per small block, a wave per large one: lz4_frame_length.h)
@@ -38,6 +41,7 @@
 #include "launch.h"
 #include "lz4_frame_format.h"
 #include "lz4_frame_length.h"
+#include "lz4f_xxh.h"
 #include "snappy_device.h"
 
 namespace fsg {
@@ -61,6 +65,9 @@ constexpr u32 kFdNsMsgs = 12, kFdNsBlocks = 13;  // answered by the fast route w
 constexpr u32 kFdBig = 14;      // length pass: blocks listed for the wave walk
 constexpr u32 kFdBigNext = 15;  // and the next of them to take
 constexpr u32 kFdLkMsgs = 16, kFdLkBlocks = 17;  // answered by the fast route for linked blocks
+// listed block entries with a checksum, pending frames with a content
+// checksum: 0 lets the checksum kernels leave at once
+constexpr u32 kFdSumBlocks = 18, kFdSumMsgs = 19;
 constexpr u64 kHead = 256;
 
 // msg_route values
@@ -175,25 +182,57 @@ __global__ __launch_bounds__(64) void lz4f_plan_kernel(const u64* __restrict__ i
   }
 }
 
-// XXH32 of each message's bytes, one lane per message
-__global__ __launch_bounds__(64) void lz4f_xxh_kernel(const u8* __restrict__ in, const u64* __restrict__ in_off,
-                                                    const u32* __restrict__ in_len, u32 n_msgs, u32* xxh) {
-  const u32 m = blockIdx.x * 64 + threadIdx.x;
-  if (m >= n_msgs) return;
-  xxh[m] = lz4f::xxh32(in + in_off[m], in_len[m]);
-}
+// ---- units of the checksum kernel (lz4f_xxh.h)
+// each body of a batch: the content checksum of compress, fsg_lz4f_xxh32_batch
+struct BodyUnits {
+  const u8* in;
+  const u64* in_off;
+  const u32* in_len;
+  u32 seed;
+  u32* xxh;
+  __device__ bool any() const { return true; }
+  __device__ bool get(u32 m, const u8** p, u64* n, u32* sd) const {
+    *p = in + in_off[m];
+    *n = in_len[m];
+    *sd = seed;
+    return true;
+  }
+  __device__ void put(u32 m, u32 h) const { xxh[m] = h; }
+};
+
+// compress, block checksums: every block entry that holds a block (the
+// prefilled rest is empty), over the bytes as stored -- the choice of
+// lz4f_assemble_kernel; the word goes to src_len, idle on this side
+struct StoredUnits {
+  const u8* in;
+  const u8* ws;
+  BlockCols c;
+  __device__ bool any() const { return true; }
+  __device__ bool get(u32 e, const u8** p, u64* n, u32* sd) const {
+    const u32 L = c.in_len[e];
+    if (L == 0) return false;
+    const u32 hl = (u32)varint32_len(L);
+    const u32 csize = c.out_len[e] - hl;
+    const bool raw = csize >= L;
+    *p = raw ? in + c.in_off[e] : ws + c.out_off[e] + hl;
+    *n = raw ? L : csize;
+    *sd = 0;
+    return true;
+  }
+  __device__ void put(u32 e, u32 h) const { c.src_len[e] = h; }
+};
 
 // One wave per message: the frame from the staged blocks.
 __global__ __launch_bounds__(64) void lz4f_assemble_kernel(const u8* __restrict__ in, const u32* __restrict__ in_len,
                                                          u8* out, const u64* __restrict__ out_off,
                                                          u32* __restrict__ out_len, i32* __restrict__ status, u32 id,
-                                                         u32 checksum, u32* hdr, MsgCols mc, BlockCols c,
+                                                         u32 flags, u32* hdr, MsgCols mc, BlockCols c,
                                                          const u8* ws) {
   const u32 m = blockIdx.x;
   const u32 lane = threadIdx.x;
   const u32 n = in_len[m];
   const u32 first = mc.first[m], nb = mc.nb[m];
-  if (first == kNoFit || lz4f::max_frame_length(n, id) > 0xFFFFFFFFull) {
+  if (first == kNoFit || lz4f::max_frame_length(n, id, flags) > 0xFFFFFFFFull) {
     if (lane == 0) {
       out_len[m] = 0;
       status[m] = kCorrupt;
@@ -201,8 +240,9 @@ __global__ __launch_bounds__(64) void lz4f_assemble_kernel(const u8* __restrict_
     return;
   }
   u8* const ob = out + out_off[m];
-  if (lane == 0) lz4f::write_header(ob, n, id, checksum != 0);
-  u64 pos = n ? 15 : 7;
+  if (lane == 0) lz4f::write_header(ob, n, id, flags);
+  const u32 bsum = (flags & lz4f::kOptBlockSums) ? 4 : 0;
+  u64 pos = n && !(flags & lz4f::kOptNoSize) ? 15 : 7;
   u32 raws = 0;
   for (u32 k0 = 0; k0 < nb; k0 += 64) {
     const u32 k = k0 + lane;
@@ -219,10 +259,13 @@ __global__ __launch_bounds__(64) void lz4f_assemble_kernel(const u8* __restrict_
       stored = raw ? L : csize;
       src = raw ? c.in_off[e] : c.out_off[e] + hl;
     }
-    const u32 sz = valid ? 4 + stored : 0;
+    const u32 sz = valid ? 4 + stored + bsum : 0;
     const u32 incl = wave_scan(sz);
     const u64 at = pos + (incl - sz);
-    if (valid) lz4f::wr32(ob + at, raw ? (L | lz4f::kRawBit) : stored);
+    if (valid) {
+      lz4f::wr32(ob + at, raw ? (L | lz4f::kRawBit) : stored);
+      if (bsum) lz4f::wr32(ob + at + 4 + stored, c.src_len[first + k]);
+    }
     raws += (u32)__builtin_popcountll(__ballot(valid && raw));
     const u32 cnt = nb - k0 < 64 ? nb - k0 : 64;
     for (u32 j = 0; j < cnt; ++j) {
@@ -236,7 +279,7 @@ __global__ __launch_bounds__(64) void lz4f_assemble_kernel(const u8* __restrict_
   if (lane == 0) {
     lz4f::wr32(ob + pos, 0);
     pos += 4;
-    if (checksum) {
+    if (flags & lz4f::kOptContentSum) {
       lz4f::wr32(ob + pos, mc.xxh[m]);
       pos += 4;
     }
@@ -387,6 +430,8 @@ __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ i
     const u64 sb = atomicAdd(reinterpret_cast<unsigned long long*>(hdr + kFdStage), (unsigned long long)need);
     if ((u64)base + nb > nb_cap || sb + need > stage_cap) return;
     list_unknown(ib, h, in_off[m], nb, base, stage_off + sb, c, chain ? kBlkChained : 0);
+    if (h.flg & lz4f::kFlgBlockSum) atomicAdd(&hdr[kFdSumBlocks], nb);
+    if (h.flg & lz4f::kFlgSum) atomicAdd(&hdr[kFdSumMsgs], 1u);
     mc.xxh[m] = xxh;
     mc.first[m] = base;
     mc.nb[m] = nb;
@@ -446,6 +491,8 @@ __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ i
     }
     ip += sz + bsum;
   }
+  if (bsum) atomicAdd(&hdr[kFdSumBlocks], nb);
+  if (h.flg & lz4f::kFlgSum) atomicAdd(&hdr[kFdSumMsgs], 1u);
   mc.first[m] = base;
   mc.nb[m] = nb;
   mc.route[m] = chain ? kRouteLinkedFast : kRouteFast;
@@ -644,21 +691,68 @@ __global__ __launch_bounds__(256) void lz4f_stage_kernel(const u8* __restrict__ 
   }
 }
 
-// One lane per block entry: the block checksum over the stored bytes, and
-// what the block decoder said.
-__global__ __launch_bounds__(64) void lz4f_verdict_kernel(const u8* __restrict__ in, BlockCols c, u32 nb_cap,
-                                                        u32* hdr) {
+// ---- units of the checksum kernel (lz4f_xxh.h) on this side
+// every listed entry with a block checksum, over the stored bytes; a word
+// that differs from the stated one marks the entry failed
+struct BlockSumUnits {
+  const u8* in;
+  const u32* hdr;
+  BlockCols c;
+  __device__ bool any() const { return hdr[kFdSumBlocks] != 0; }
+  __device__ bool get(u32 e, const u8** p, u64* n, u32* sd) const {
+    const u32 f = c.flags[e];
+    if (!(f & kBlkListed) || !(f & kBlkSum)) return false;
+    *p = in + c.src_off[e];
+    *n = c.src_len[e];
+    *sd = 0;
+    return true;
+  }
+  __device__ void put(u32 e, u32 h) const {
+    if (h != lz4f::rd32(in + c.src_off[e] + c.src_len[e])) c.flags[e] |= kBlkFailed;
+  }
+};
+
+// every frame pending on a fast route whose descriptor (valid: index parsed
+// it) flags a content checksum, over the bytes in its slot: the content size,
+// or where the last block ends.  xxh[m] held the stated word; computed ^
+// stated stays there, 0 when they agree.
+struct ContentUnits {
+  const u8* in;
+  const u64* in_off;
+  const u8* out;
+  const u64* out_off;
+  const u32* hdr;
+  MsgCols mc;
+  BlockCols c;
+  __device__ bool any() const { return hdr[kFdSumMsgs] != 0; }
+  __device__ bool get(u32 m, const u8** p, u64* n, u32* sd) const {
+    const u32 route = mc.route[m];
+    const bool sized = route == kRouteFast || route == kRouteLinkedOk;
+    if (!sized && route != kRouteNoSizeFast && route != kRouteLinkedNsOk) return false;
+    const u8* ib = in + in_off[m];
+    if (!(ib[4] & lz4f::kFlgSum)) return false;
+    if (sized) {
+      *n = (u64)lz4f::rd32(ib + 6) | (u64)lz4f::rd32(ib + 10) << 32;
+    } else {
+      const u32 last = mc.first[m] + mc.nb[m] - 1;
+      *n = c.out_off[last] + c.out_cap[last] - out_off[m];
+    }
+    *p = out + out_off[m];
+    *sd = 0;
+    return true;
+  }
+  __device__ void put(u32 m, u32 h) const { mc.xxh[m] ^= h; }
+};
+
+// One lane per block entry: what the checksum kernel and the block decoder
+// said.
+__global__ __launch_bounds__(64) void lz4f_verdict_kernel(BlockCols c, u32 nb_cap, u32* hdr) {
   const u32 e = blockIdx.x * 64 + threadIdx.x;
   if (e >= nb_cap) return;
   const u32 f = c.flags[e];
   const bool listed = f & kBlkListed;
   bool fail = false;
-  if (listed && (f & kBlkSum)) {
-    const u8* src = in + c.src_off[e];
-    const u32 sz = c.src_len[e];
-    fail = lz4f::xxh32(src, sz) != lz4f::rd32(src + sz);
-  }
-  if (listed && !(f & kBlkRaw)) fail = fail || c.status[e] != kOk || c.out_len[e] != c.out_cap[e];
+  if (listed && !(f & kBlkRaw)) fail = c.status[e] != kOk || c.out_len[e] != c.out_cap[e];
   if (fail) c.flags[e] = f | kBlkFailed;
   count_lanes(&hdr[kFdSums], listed && (f & kBlkSum));
 }
@@ -689,7 +783,7 @@ __global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ 
     lz4f::Header h;
     lz4f::parse_header(ib, in_len[m], &h);
     if (ok && (h.flg & lz4f::kFlgSum)) {
-      ok = lz4f::xxh32(ob, h.size) == mc.xxh[m];
+      ok = mc.xxh[m] == 0;  // (the checksum kernel left computed ^ stated)
       sums = 1;
     }
     if (ok) {
@@ -709,7 +803,7 @@ __global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ 
     lz4f::Header h;
     lz4f::parse_header(ib, in_len[m], &h);
     if (ok && (h.flg & lz4f::kFlgSum)) {
-      ok = lz4f::xxh32(ob, total) == mc.xxh[m];
+      ok = mc.xxh[m] == 0;
       sums = 1;
     }
     if (ok) {
@@ -903,13 +997,21 @@ hipError_t launch_lz4f_encode(const u8* in, const u64* in_off, const u32* in_len
   e = launch_lz4_encode(in, c.in_off, c.in_len, p.nb_cap, w, c.out_off, c.out_len, c.status, w + p.off_inner,
                         p.inner_bytes, wave_min, stream);
   if (e != hipSuccess) return e;
-  if (flags & 1) {
-    lz4f_xxh_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, mc.xxh);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+  // the checksum kernel: the messages, and the entries' bytes as stored
+  if (flags & lz4f::kOptContentSum) {
+    if ((e = launch_xxh_quads(BodyUnits{in, in_off, in_len, 0u, mc.xxh}, n_msgs, stream)) != hipSuccess) return e;
   }
-  lz4f_assemble_kernel<<<n_msgs, 64, 0, stream>>>(in, in_len, out, out_off, out_len, status, id, flags & 1, hdr, mc, c,
+  if (flags & lz4f::kOptBlockSums) {
+    if ((e = launch_xxh_quads(StoredUnits{in, w, c}, p.nb_cap, stream)) != hipSuccess) return e;
+  }
+  lz4f_assemble_kernel<<<n_msgs, 64, 0, stream>>>(in, in_len, out, out_off, out_len, status, id, flags, hdr, mc, c,
                                                   w);
   return hipGetLastError();
+}
+
+hipError_t launch_lz4f_xxh32(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u32 seed, u32* xxh,
+                             hipStream_t stream) {
+  return launch_xxh_quads(BodyUnits{in, in_off, in_len, seed, xxh}, n_msgs, stream);
 }
 
 hipError_t launch_lz4f_content_sizes(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* sizes,
@@ -1004,8 +1106,14 @@ hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len
     e = launch_lz4_decode2(w, c.in_off, c.in_len, p.nb_cap, out, c.out_off, c.out_cap, c.out_len, c.status,
                            w + p.off_inner, p.inner_bytes, stream, nullptr, linked_fast ? &chains : nullptr);
     if (e != hipSuccess) return e;
-    lz4f_verdict_kernel<<<(p.nb_cap + 63) / 64, 64, 0, stream>>>(in, c, p.nb_cap, hdr);
+    // the checksum kernel: block checksums of the listed entries, then (the
+    // chains' results and the blocks' places are known) the content checksums
+    // of the pending frames; each leaves at once when index counted none
+    if ((e = launch_xxh_quads(BlockSumUnits{in, hdr, c}, p.nb_cap, stream)) != hipSuccess) return e;
+    lz4f_verdict_kernel<<<(p.nb_cap + 63) / 64, 64, 0, stream>>>(c, p.nb_cap, hdr);
     if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = launch_xxh_quads(ContentUnits{in, in_off, out, out_off, hdr, mc, c}, n_msgs, stream)) != hipSuccess)
+      return e;
     inner_fallback = reinterpret_cast<const u32*>(w + p.off_inner) + 3;  // lz4_decode2.hip: its fallback counter
   }
   lz4f_finish_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_cap, out_len,

@@ -106,21 +106,56 @@ LZ4F_HD uint32_t frame_block_id(uint64_t n, uint32_t id) {
   return p;
 }
 
-// The descriptor the compressor writes (independent blocks, no block
-// checksums; the content size unless n is 0, which LZ4F_compressFrame reads as
-// "unknown"); returns its length, 7 or 15.
-LZ4F_HD uint32_t write_header(uint8_t* p, uint64_t n, uint32_t id, bool checksum) {
+// n bytes forward, 16 at a time then singly; source and destination apart
+// (raw blocks, literals)
+LZ4F_HD void copy_bytes(uint8_t* d, const uint8_t* s, uint64_t n) {
+  uint64_t k = 0;
+  for (; k + 16 <= n; k += 16) __builtin_memcpy(d + k, s + k, 16);
+  for (; k < n; ++k) d[k] = s[k];
+}
+
+// ---- the frame writer: what the compressors, device and host, share
+// compress flags (FSG_LZ4F_FLAG_* of include/flare_lz4_gpu.h); the callers reject other bits
+constexpr uint32_t kOptContentSum = 1, kOptBlockSums = 2, kOptNoSize = 4;
+
+// The descriptor the compressor writes (independent blocks; block checksums
+// and a content checksum as the flags ask; the content size unless kOptNoSize
+// is set or n is 0, which LZ4F_compressFrame reads as "unknown"); returns its
+// length, 7 or 15.  BD holds the smallest-id rule's id with or without a size.
+LZ4F_HD uint32_t write_header(uint8_t* p, uint64_t n, uint32_t id, uint32_t flags) {
+  const bool size = n && !(flags & kOptNoSize);
   wr32(p, kMagic);
-  p[4] = (uint8_t)(0x40 | kFlgIndep | (n ? kFlgSize : 0) | (checksum ? kFlgSum : 0));
+  p[4] = (uint8_t)(0x40 | kFlgIndep | ((flags & kOptBlockSums) ? kFlgBlockSum : 0) | (size ? kFlgSize : 0) |
+                   ((flags & kOptContentSum) ? kFlgSum : 0));
   p[5] = (uint8_t)(frame_block_id(n, id) << 4);
   uint32_t len = 6;
-  if (n) {
+  if (size) {
     wr32(p + 6, (uint32_t)n);
     wr32(p + 10, (uint32_t)(n >> 32));
     len = 14;
   }
   p[len] = (uint8_t)(xxh32(p + 4, len - 4) >> 8);
   return len + 1;
+}
+
+// One block at p: the size word, the bytes as stored (the encoded block, or
+// the input bytes when `raw`), and with kOptBlockSums the XXH32 of the bytes
+// as stored; returns the bytes written.  The serial writer (the host codec);
+// the device writes the same fields a wave per message.
+LZ4F_HD uint64_t write_block(uint8_t* p, const uint8_t* stored, uint32_t len, bool raw, uint32_t flags) {
+  wr32(p, raw ? (len | kRawBit) : len);
+  copy_bytes(p + 4, stored, len);
+  if (!(flags & kOptBlockSums)) return 4ull + len;
+  wr32(p + 4 + len, xxh32(stored, len));
+  return 8ull + len;
+}
+
+// The end mark, and the content checksum when kOptContentSum asks for it.
+LZ4F_HD uint32_t write_end(uint8_t* p, uint32_t flags, uint32_t content_xxh) {
+  wr32(p, 0);
+  if (!(flags & kOptContentSum)) return 4;
+  wr32(p + 4, content_xxh);
+  return 8;
 }
 
 // Frame bound for the compressor's settings: descriptor 15, a size word per
@@ -131,16 +166,15 @@ LZ4F_HD uint64_t max_frame_length(uint64_t n, uint32_t id) {
   const uint64_t bs = block_bytes(id);
   return 15 + 4 * ((n + bs - 1) / bs) + n + 4 + 4;
 }
-
-// ---- blocks
-// n bytes forward, 16 at a time then singly; source and destination apart
-// (raw blocks, literals)
-LZ4F_HD void copy_bytes(uint8_t* d, const uint8_t* s, uint64_t n) {
-  uint64_t k = 0;
-  for (; k + 16 <= n; k += 16) __builtin_memcpy(d + k, s + k, 16);
-  for (; k < n; ++k) d[k] = s[k];
+// And with the compress flags: a checksum word per block more with
+// kOptBlockSums.  (kOptNoSize makes a frame 8 bytes shorter; the bound does
+// not follow it.)
+LZ4F_HD uint64_t max_frame_length(uint64_t n, uint32_t id, uint32_t flags) {
+  const uint64_t bs = block_bytes(id);
+  return max_frame_length(n, id) + ((flags & kOptBlockSums) ? 4 * ((n + bs - 1) / bs) : 0);
 }
 
+// ---- blocks
 // Decoded length of a block from its sequences' lengths alone: the sequence
 // whose literals end at the block's last byte is the last one.  false: no such
 // sequence, or more than `limit` bytes.

@@ -114,6 +114,14 @@ size_t fsh_cpu_lz4f_compress(const uint8_t* in, size_t n, uint8_t* out, int bloc
   return flare::lz4::cpu::CompressFrame(in, n, out, block_size_id, content_checksum != 0);
 }
 
+size_t fsh_lz4f_max_frame_length_flags(size_t n, int block_size_id, uint32_t flags) {
+  return flare::lz4::cpu::MaxFrameLength(n, block_size_id, flags);
+}
+
+size_t fsh_cpu_lz4f_compress_flags(const uint8_t* in, size_t n, uint8_t* out, int block_size_id, uint32_t flags) {
+  return flare::lz4::cpu::CompressFrame(in, n, out, block_size_id, flags);
+}
+
 int fsh_cpu_lz4f_uncompress(const uint8_t* in, size_t n, uint8_t* out, size_t cap, uint32_t* out_len) {
   static const int kCode[4] = {1, 0, -1, -2};  // FSG_OK, FSG_CORRUPT, FSG_BAD_HEADER, FSG_SLOT_TOO_SMALL
   return kCode[flare::lz4::cpu::DecompressFrame(in, n, out, cap, out_len)];

@@ -230,27 +230,28 @@ size_t MaxFrameLength(size_t n, int block_size_id) {
   return lz4f::max_frame_length(n, static_cast<uint32_t>(block_size_id));
 }
 
-size_t CompressFrame(const uint8_t* in, size_t n, uint8_t* out, int block_size_id, bool content_checksum) {
-  if (block_size_id < 4 || block_size_id > 7) return 0;
+size_t MaxFrameLength(size_t n, int block_size_id, uint32_t flags) {
+  if (block_size_id < 4 || block_size_id > 7 || flags > 7) return 0;
+  return lz4f::max_frame_length(n, static_cast<uint32_t>(block_size_id), flags);
+}
+
+size_t CompressFrame(const uint8_t* in, size_t n, uint8_t* out, int block_size_id, uint32_t flags) {
+  if (block_size_id < 4 || block_size_id > 7 || flags > 7) return 0;
   const uint32_t id = static_cast<uint32_t>(block_size_id);
   const size_t bs = lz4f::block_bytes(id);
-  size_t op = lz4f::write_header(out, n, id, content_checksum);
-  std::vector<uint8_t> blk(BlockBound(bs));
+  size_t op = lz4f::write_header(out, n, id, flags);
+  std::vector<uint8_t> blk(BlockBound(n < bs ? n : bs));
   for (size_t ip = 0; ip < n; ip += bs) {
     const size_t len = n - ip < bs ? n - ip : bs;
     const size_t c = CompressBlock(in + ip, len, blk.data());
     const bool raw = c >= len;  // a block that does not shrink is stored as it is
-    lz4f::wr32(out + op, raw ? static_cast<uint32_t>(len) | lz4f::kRawBit : static_cast<uint32_t>(c));
-    std::memcpy(out + op + 4, raw ? in + ip : blk.data(), raw ? len : c);
-    op += 4 + (raw ? len : c);
+    op += lz4f::write_block(out + op, raw ? in + ip : blk.data(), static_cast<uint32_t>(raw ? len : c), raw, flags);
   }
-  lz4f::wr32(out + op, 0);
-  op += 4;
-  if (content_checksum) {
-    lz4f::wr32(out + op, lz4f::xxh32(in, n));
-    op += 4;
-  }
-  return op;
+  return op + lz4f::write_end(out + op, flags, (flags & kFrameContentChecksum) ? lz4f::xxh32(in, n) : 0);
+}
+
+size_t CompressFrame(const uint8_t* in, size_t n, uint8_t* out, int block_size_id, bool content_checksum) {
+  return CompressFrame(in, n, out, block_size_id, content_checksum ? kFrameContentChecksum : 0u);
 }
 
 int DecompressFrame(const uint8_t* in, size_t n, uint8_t* out, size_t cap, uint32_t* out_len) {

@@ -48,6 +48,14 @@ size_t MaxFrameLength(size_t n, int block_size_id);
 // The bytes of LZ4F_compressFrame (independent blocks, content size, level 0,
 // no block checksums) into out (MaxFrameLength bytes); returns the length.
 size_t CompressFrame(const uint8_t* in, size_t n, uint8_t* out, int block_size_id, bool content_checksum);
+// The same with a flags word (FSG_LZ4F_FLAG_*; `true` above is bit 0): a
+// content checksum, a checksum behind every block over its bytes as stored,
+// no content size -- the frame preferences of LZ4F_compressFrame, byte for
+// byte.  out: MaxFrameLength(n, id, flags) bytes, 4 per block more with
+// kFrameBlockChecksums.  Both return 0 for a flags word with any other bit.
+constexpr uint32_t kFrameContentChecksum = 1, kFrameBlockChecksums = 2, kFrameNoContentSize = 4;
+size_t MaxFrameLength(size_t n, int block_size_id, uint32_t flags);
+size_t CompressFrame(const uint8_t* in, size_t n, uint8_t* out, int block_size_id, uint32_t flags);
 // One frame to out (cap bytes): 0 ok, 1 corrupt, 2 bad header, 3 content size
 // above cap (the FSG_* status words); *out_len as d_out_len of the GPU call.
 int DecompressFrame(const uint8_t* in, size_t n, uint8_t* out, size_t cap, uint32_t* out_len);

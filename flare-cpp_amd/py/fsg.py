@@ -49,6 +49,8 @@ Lz4fDecodeReport = _report_struct("Lz4fDecodeReport", (
     "serial_forced", "checksummed_units", "inner_fallback_blocks", "block_entries", "fast_nosize_messages",
     "fast_nosize_blocks", "fast_linked_messages", "fast_linked_blocks"))
 LZ4F_NO_CONTENT_SIZE = 0xFFFFFFFFFFFFFFFF
+# fsg_lz4f_compress_batch_flags' flags (FSG_LZ4F_FLAG_*)
+LZ4F_FLAG_CONTENT_CHECKSUM, LZ4F_FLAG_BLOCK_CHECKSUMS, LZ4F_FLAG_NO_CONTENT_SIZE = 1, 2, 4
 PATH_MAIN, PATH_SINGLE_DESIGN, PATH_NO_WORKSPACE, PATH_FORCED = 0, 1, 2, 3
 
 _SIGS = {
@@ -90,8 +92,11 @@ _SIGS = {
     "fsg_lz4_decompress_batch_2s": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
                                                _vp]),
     "fsg_lz4f_max_frame_length": (_sz, [_sz, _u32]),
+    "fsg_lz4f_max_frame_length_flags": (_sz, [_sz, _u32, _u32]),
+    "fsg_lz4f_xxh32_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp]),
     "fsg_lz4f_compress_workspace_bytes": (_sz, [_u32, _u64, _u32]),
     "fsg_lz4f_compress_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _sz, _vp]),
+    "fsg_lz4f_compress_batch_flags": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _sz, _vp]),
     "fsg_lz4f_decompress_workspace_bytes": (_sz, [_u32, _u64]),
     "fsg_lz4f_decompress_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "fsg_lz4f_content_sizes_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp]),
@@ -116,7 +121,8 @@ _OPTIONAL = {"fsg_decompress_batch_2s", "fsg_decompress_batch_partial", "fsg_dec
              "fsg_compress_report", "fsg_lz4_decompress_report", "fsg_lz4_compress_report",
              "fsg_lz4f_max_frame_length", "fsg_lz4f_compress_workspace_bytes", "fsg_lz4f_compress_batch",
              "fsg_lz4f_decompress_workspace_bytes", "fsg_lz4f_decompress_batch", "fsg_lz4f_content_sizes_batch",
-             "fsg_lz4f_compress_report", "fsg_lz4f_decompress_report", "fsg_lz4f_decoded_lengths_batch"}
+             "fsg_lz4f_compress_report", "fsg_lz4f_decompress_report", "fsg_lz4f_decoded_lengths_batch",
+             "fsg_lz4f_max_frame_length_flags", "fsg_lz4f_xxh32_batch", "fsg_lz4f_compress_batch_flags"}
 
 
 def load_gpu_lib(path: Path | None = None) -> ctypes.CDLL:
@@ -302,14 +308,30 @@ class SnappyGPU:
         return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device or f"cuda:{self.device}")
 
     def lz4f_compress(self, d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_len, d_status, workspace,
-                      block_size_id=4, checksum=False, stream=None):
-        """fsg_lz4f_compress_batch: standard LZ4 frames, slots of
-        fsg_lz4f_max_frame_length(len, block_size_id) bytes."""
+                      block_size_id=4, checksum=False, stream=None, flags=None):
+        """fsg_lz4f_compress_batch: standard LZ4 frames, with a content
+        checksum when `checksum`.  With `flags` (LZ4F_FLAG_* bits) it is
+        fsg_lz4f_compress_batch_flags, with slots of
+        lz4f_max_frame_length_flags(len, block_size_id, flags) bytes."""
         ws = 0 if workspace is None else workspace.numel() * workspace.element_size()
-        self._check(self.lib.fsg_lz4f_compress_batch(
+        name = "fsg_lz4f_compress_batch" if flags is None else "fsg_lz4f_compress_batch_flags"
+        if flags is None:
+            flags = LZ4F_FLAG_CONTENT_CHECKSUM if checksum else 0
+        self._check(getattr(self.lib, name)(
             _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len),
-            _ptr(d_status), block_size_id, 1 if checksum else 0, _ptr(workspace), ws, self._stream(stream)),
-            "fsg_lz4f_compress_batch")
+            _ptr(d_status), block_size_id, flags, _ptr(workspace), ws, self._stream(stream)), name)
+
+    def lz4f_max_frame_length_flags(self, n, block_size_id=4, flags=0):
+        """fsg_lz4f_max_frame_length_flags: the slot size of a compress call
+        with `flags` (4 bytes per block more with LZ4F_FLAG_BLOCK_CHECKSUMS)."""
+        return self.lib.fsg_lz4f_max_frame_length_flags(n, block_size_id, flags)
+
+    def lz4f_xxh32(self, d_in, d_in_off, d_in_len, n, d_xxh, seed=0, stream=None):
+        """fsg_lz4f_xxh32_batch: XXH32 of each body into d_xxh (int32 /
+        uint32, n entries), no workspace."""
+        self._check(self.lib.fsg_lz4f_xxh32_batch(
+            _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, seed, _ptr(d_xxh), self._stream(stream)),
+            "fsg_lz4f_xxh32_batch")
 
     def lz4f_decompress_workspace(self, n, total_in_bytes, device=None):
         import torch

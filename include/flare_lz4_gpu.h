@@ -162,13 +162,36 @@ int fsg_lz4_compress_report(const void *header_host_copy, uint32_t n_msgs,
  * is set.
  *
  * The compressor writes exactly the bytes of LZ4F_compressFrame (liblz4
- * 1.9.x) with blockMode = independent, blockSizeID as asked for, contentSize =
- * n, compression level 0, no block checksums, a content checksum when flag
- * bit 0 asks for it: every block is LZ4_compress_default of its bytes, stored
- * raw when that is not shorter than they are.  As there, BD holds the smallest
- * id, up to the one asked for, whose block holds the whole message (a message
- * of at most 64 KiB says id 4 whatever was asked).  An empty message has no C.Size
- * field and no blocks (liblz4 reads contentSize 0 as "unknown"): 11 bytes.
+ * 1.9.x) with blockMode = independent, blockSizeID as asked for, compression
+ * level 0, and the three frame preferences the flags of
+ * fsg_lz4f_compress_batch_flags name: every block is
+ * LZ4_compress_default of its bytes, stored raw when that is not shorter than
+ * they are.
+ *   FSG_LZ4F_FLAG_CONTENT_CHECKSUM (contentChecksumFlag): C.Checksum is set
+ *     and the XXH32 of the message follows the end mark.
+ *   FSG_LZ4F_FLAG_BLOCK_CHECKSUMS (blockChecksumFlag): B.Checksum is set and
+ *     every block is followed by the XXH32 of its bytes as stored -- the
+ *     encoded block, or the message's own bytes when the block is stored raw.
+ *   FSG_LZ4F_FLAG_NO_CONTENT_SIZE (contentSize = 0): no C.Size bit and no
+ *     size field, 8 bytes less; without it contentSize = n.
+ * Nothing else depends on the flags: the blocks, the size words and BD are
+ * the same for all eight combinations.  With bits 0 and 2 this is what the lz4
+ * command writes by default.  As in liblz4, BD holds the smallest id, up to
+ * the one asked for, whose block holds the whole message (a message of at most
+ * 64 KiB says id 4 whatever was asked), with or without a content size.  An
+ * empty message has no C.Size field and no blocks (liblz4 reads contentSize 0
+ * as "unknown"): 11 bytes, 15 with a content checksum.  A flags word with a
+ * bit above the three is FSG_ERR_INVALID_ARG.  fsg_lz4f_compress_batch, the
+ * call from before bits 1 and 2 had a meaning, takes bit 0 alone and keeps
+ * answering FSG_ERR_INVALID_ARG to every other bit, so nothing changes for a
+ * caller of it; with flags 0 or 1 the two calls are the same call.
+ *
+ * Checksums.  Every XXH32 over message or block bytes -- the content and block
+ * checksums the compressor writes, the block checksums of the entries a fast
+ * route lists and the content checksum of every frame pending on one in the
+ * decompressor, fsg_lz4f_xxh32_batch -- is computed by one kernel, a quad of
+ * lanes per byte range (csrc/lz4f_xxh.h).  The serial decoder and the
+ * descriptor's HC byte use the serial text (csrc/lz4_frame_format.h).
  *
  * The decompressor accepts one frame per body; bytes after it are
  * FSG_CORRUPT.  FSG_BAD_HEADER: a bad magic number (the skippable and legacy
@@ -233,14 +256,32 @@ int fsg_lz4_compress_report(const void *header_host_copy, uint32_t n_msgs,
  * status either.  Frames it answers are counted in fast_linked_messages, not
  * in fast_messages, fast_nosize_messages or serial_linked.
  *
- * "What a *_batch call writes" holds for both calls, every status and route.
- * Slots: fsg_lz4f_max_frame_length(d_in_len[i], id) for compress. */
+ * "What a *_batch call writes" holds for both calls, every status, route and
+ * flag combination, and for fsg_lz4f_xxh32_batch (exactly n_msgs words).
+ * Slots for compress: fsg_lz4f_max_frame_length(d_in_len[i], id) for
+ * fsg_lz4f_compress_batch, and for fsg_lz4f_compress_batch_flags when flag
+ * bit 1 (block checksums) is clear; fsg_lz4f_max_frame_length_flags(
+ * d_in_len[i], id, flags) when it is set: a slot of the smaller size is too
+ * small for such a call, and the call does not check it. */
+
+/* fsg_lz4f_compress_batch_flags' flags; any other bit is FSG_ERR_INVALID_ARG */
+#define FSG_LZ4F_FLAG_CONTENT_CHECKSUM 1u
+#define FSG_LZ4F_FLAG_BLOCK_CHECKSUMS 2u
+#define FSG_LZ4F_FLAG_NO_CONTENT_SIZE 4u
 
 /* n + 4 * ceil(n / block size) + 23: descriptor (15), a size word per block,
  * the bytes (a block that does not shrink is stored raw), end mark (4),
  * content checksum (4).  LZ4F_compressFrameBound gives 4 more (it counts the
  * largest descriptor, 19 bytes with a DictID).  0 for an id outside 4..7. */
 size_t fsg_lz4f_max_frame_length(size_t n, uint32_t block_size_id);
+
+/* The same for a compress call with `flags`: 4 bytes per block more when
+ * FSG_LZ4F_FLAG_BLOCK_CHECKSUMS is set, otherwise the value above (a frame
+ * without a content size is 8 bytes shorter; the bound does not follow it);
+ * 0 for an id outside 4..7 or a flags word with an undefined bit.
+ * The slot size for calls with that bit; reached exactly by a message of
+ * incompressible bytes with bits 0 and 1 and a content size. */
+size_t fsg_lz4f_max_frame_length_flags(size_t n, uint32_t block_size_id, uint32_t flags);
 
 /* Workspace of fsg_lz4f_compress_batch for a batch of n_msgs messages and
  * total_in_bytes input bytes in all: block columns and the block encoder's
@@ -251,8 +292,11 @@ size_t fsg_lz4f_max_frame_length(size_t n, uint32_t block_size_id);
  * FSG_CORRUPT with d_out_len 0 (nothing else changes). */
 size_t fsg_lz4f_compress_workspace_bytes(uint32_t n_msgs, uint64_t total_in_bytes, uint32_t block_size_id);
 
-/* Batched frame compress, columns as fsg_lz4_compress_batch.  flags bit 0:
- * write a content checksum.  The blocks go through the block encoders of
+/* Batched frame compress, columns as fsg_lz4_compress_batch.  flags:
+ * FSG_LZ4F_FLAG_CONTENT_CHECKSUM or 0; every other bit is
+ * FSG_ERR_INVALID_ARG (fsg_lz4f_compress_batch_flags below takes all three).
+ * Slots of fsg_lz4f_max_frame_length.  No checksum kernel is launched when
+ * flags is 0.  The blocks go through the block encoders of
  * fsg_lz4_compress_batch with that call's routing; option lz4f_block_wave_min
  * (FSG_L4F_BLOCK_WAVE_MIN) is their wave threshold, -1 (default) the
  * automatic rule applied to the workspace's block entries.  A NULL workspace
@@ -265,6 +309,18 @@ int fsg_lz4f_compress_batch(const uint8_t *d_in, const uint64_t *d_in_off,
                             uint32_t block_size_id, uint32_t flags,
                             void *d_workspace, size_t workspace_bytes,
                             void *stream);
+
+/* The same call with the whole flags word: the FSG_LZ4F_FLAG_* bits above
+ * ("The compressor writes ..."); slots as "Slots" there says.  The workspace
+ * is that of fsg_lz4f_compress_batch and does not depend on the flags, and no
+ * checksum kernel is launched when bits 0 and 1 are clear. */
+int fsg_lz4f_compress_batch_flags(const uint8_t *d_in, const uint64_t *d_in_off,
+                                  const uint32_t *d_in_len, uint32_t n_msgs,
+                                  uint8_t *d_out, const uint64_t *d_out_off,
+                                  uint32_t *d_out_len, int32_t *d_status,
+                                  uint32_t block_size_id, uint32_t flags,
+                                  void *d_workspace, size_t workspace_bytes,
+                                  void *stream);
 
 /* Workspace of fsg_lz4f_decompress_batch: block columns for n_msgs +
  * total_in_bytes / 256 blocks (a full 64 KiB block has at least 257 bytes),
@@ -285,6 +341,16 @@ int fsg_lz4f_decompress_batch(const uint8_t *d_in, const uint64_t *d_in_off,
                               const uint32_t *d_out_cap, uint32_t *d_out_len,
                               int32_t *d_status, void *d_workspace,
                               size_t workspace_bytes, void *stream);
+
+/* XXH32 (seed `seed`) of each body, d_xxh[i] for [d_in + d_in_off[i],
+ * + d_in_len[i]), on the checksum kernel of the frame calls: a quad of lanes
+ * per body, 16 bodies per wave.  Bodies may start at any byte address and may
+ * be empty; no byte outside a body is read.  No workspace; exactly n_msgs
+ * words are written.  For a caller who checksums frames it did not decode
+ * here; n_msgs == 0 succeeds and launches nothing. */
+int fsg_lz4f_xxh32_batch(const uint8_t *d_in, const uint64_t *d_in_off,
+                         const uint32_t *d_in_len, uint32_t n_msgs,
+                         uint32_t seed, uint32_t *d_xxh, void *stream);
 
 /* The content size each body's descriptor states, for sizing slots
  * (fsg_uncompressed_lengths_batch's counterpart): d_content_size[i] = the

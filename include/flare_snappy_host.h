@@ -114,6 +114,13 @@ int fsh_register_lz4(void);
 size_t fsh_lz4f_max_frame_length(size_t n, int block_size_id);
 /* frame of n bytes into out; its length (0 for a bad block size id) */
 size_t fsh_cpu_lz4f_compress(const uint8_t* in, size_t n, uint8_t* out, int block_size_id, int content_checksum);
+/* the same with the flags word of fsg_lz4f_compress_batch_flags (FSG_LZ4F_FLAG_*:
+ * 1 content checksum, 2 block checksums, 4 no content size; both
+ * functions return 0 for a word with any other bit, as for a bad block size
+ * id); out holds fsh_lz4f_max_frame_length_flags(n, id, flags) bytes,
+ * which is 4 per block more than fsh_lz4f_max_frame_length with bit 1 set */
+size_t fsh_lz4f_max_frame_length_flags(size_t n, int block_size_id, uint32_t flags);
+size_t fsh_cpu_lz4f_compress_flags(const uint8_t* in, size_t n, uint8_t* out, int block_size_id, uint32_t flags);
 /* frame to out (cap bytes): 1 ok, 0 corrupt, -1 bad header, -2 content size
  * above cap; *out_len = decoded length (ok) or min(content size, 2^32-1) (-2) */
 int fsh_cpu_lz4f_uncompress(const uint8_t* in, size_t n, uint8_t* out, size_t cap, uint32_t* out_len);

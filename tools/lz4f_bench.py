@@ -9,6 +9,8 @@ per call.  One JSON line per row.
     python tools/lz4f_bench.py --no-size [--rows 16x4m@7,16x4m@7c,c3,1x64k] [--bid 4] [--checksum 1]
     python tools/lz4f_bench.py --length-pass
     python tools/lz4f_bench.py --linked [--rows 16x4m@4,16x4m@7,4096x128k@4,1x128k@4] [--sys-linked 1]
+    python tools/lz4f_bench.py --sums [--rows 16x4m@4,16x4m@7,c3@4]
+    python tools/lz4f_bench.py --xxh [--rows 1x4m,16x4m,1024x64k,c3]
 
 Rows: 16x4m (16 x 4 MiB: 64 independent blocks a body, where the format adds
 parallelism) and c3 (65,536 x 64 KiB: one block a body, the cost of the plan,
@@ -33,6 +35,12 @@ lz4f_linked_fast and lz4f_nosize_fast both 0 (the serial decoder) and both 1
 serial figure alone.  --sys-linked 1: one more row, 16 x 4 MiB at id 4 written
 by the system liblz4 with LZ4F_blockLinked (copies into history included);
 reported as missing where liblz4 is not installed.
+
+--sums: the rows' sized frames written without checksums, with a content
+checksum, with block checksums and with both (fsg_lz4f_compress_batch_flags'
+flags), compress and then decompress, the variants alternating launch by launch
+in one process, so a checksum's share is a difference of two figures of one
+line.  --xxh: fsg_lz4f_xxh32_batch alone, in ms and GiB/s.
 """
 import argparse
 import json
@@ -388,8 +396,103 @@ def length_pass(torch, codec, warmup, launches, limit_bytes=2 << 30):
     fsg.set_option("lz4f_length_wave_min", saved)
 
 
+SUM_FLAGS = {"none": 0, "content": 1, "block": 2, "both": 3}
+
+
+def sums_row(torch, codec, name, bid, warmup, launches, only=None, time_compress=True):
+    """The row's sized frames without checksums, with a content checksum, with
+    block checksums and with both, compress and decompress, the variants
+    alternating launch by launch in one process: a checksum's share is the
+    difference of two figures of this line.  A library without
+    fsg_lz4f_max_frame_length_flags gives "none" and "content" alone."""
+    dev = torch.device("cuda", 0)
+    lib = codec.lib
+    n, size = ROWS[name]
+    batch = fsg.make_batch(fsg.KIND_TEXT, np.full(n, size, np.uint32))
+    raw = batch.total
+    H = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    s = torch.cuda.current_stream()
+    d_raw, d_ro, d_rl = H(batch.data), H(batch.offsets), H(batch.lens)
+    flagged = hasattr(lib, "fsg_lz4f_max_frame_length_flags")
+    kinds = [k for k, f in SUM_FLAGS.items() if (flagged or f < 2) and (only is None or k in only)]
+    bound = (lambda x: lib.fsg_lz4f_max_frame_length_flags(x, bid, 3)) if flagged else \
+        (lambda x: lib.fsg_lz4f_max_frame_length(x, bid))
+    f_off, f_tot = fsg.slot_offsets(np.array([bound(int(x)) for x in batch.lens], np.uint64))
+    d_fo = H(f_off)
+    ws = codec.lz4f_compress_workspace(n, raw, bid)
+    bufs = {k: (torch.zeros(f_tot, dtype=torch.uint8, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
+                torch.zeros(n, dtype=torch.int32, device=dev)) for k in kinds}
+
+    def enc(k):
+        d_f, d_fl, d_st = bufs[k]
+        if flagged:
+            return lambda: codec.lz4f_compress(d_raw, d_ro, d_rl, n, d_f, d_fo, d_fl, d_st, ws, block_size_id=bid,
+                                               flags=SUM_FLAGS[k], stream=s)
+        return lambda: codec.lz4f_compress(d_raw, d_ro, d_rl, n, d_f, d_fo, d_fl, d_st, ws, block_size_id=bid,
+                                           checksum=bool(SUM_FLAGS[k]), stream=s)
+
+    out = {"mode": "sums", "row": name, "n": n, "size": size, "block_size_id": bid, "launches": launches,
+           "warmup": warmup, "raw_bytes": raw, "has_flags": flagged}
+    if time_compress:
+        for k, m in zip(kinds, alternate(torch, s, [enc(k) for k in kinds], warmup, launches)):
+            out["compress_" + k] = m
+    else:  # (the frames are needed all the same)
+        for k in kinds:
+            enc(k)()
+        torch.cuda.synchronize()
+    ok = all(int((bufs[k][2] != 0).sum().item()) == 0 for k in kinds)
+    del ws
+    torch.cuda.empty_cache()
+    d_out = torch.full((raw,), 0xA5, dtype=torch.uint8, device=dev)
+    d_ol = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+    dws = codec.lz4f_decompress_workspace(n, int(f_tot))
+
+    def dec(k):
+        d_f, d_fl, _ = bufs[k]
+        return lambda: codec.lz4f_decompress(d_f, d_fo, d_fl, n, d_out, d_ro, d_rl, d_ol, d_st, dws, stream=s)
+
+    for k, m in zip(kinds, alternate(torch, s, [dec(k) for k in kinds], warmup, launches)):
+        out["decompress_" + k] = m
+    for k in kinds:
+        d_out.fill_(0xA5)
+        dec(k)()
+        torch.cuda.synchronize()
+        ok = ok and int((d_st != 0).sum().item()) == 0 and bool(torch.equal(d_out, d_raw))
+        out["checksummed_units_" + k] = codec.lz4f_decompress_report(dws, n)["checksummed_units"]
+    out["ok"] = ok
+    print(json.dumps(out), flush=True)
+
+
+XXH_ROWS = {"1x4m": (1, 4 << 20), "16x4m": (16, 4 << 20), "1024x64k": (1024, 64 << 10), "c3": (65536, 64 << 10)}
+
+
+def xxh_row(torch, codec, name, warmup, launches):
+    """fsg_lz4f_xxh32_batch alone on the row's bodies."""
+    dev = torch.device("cuda", 0)
+    n, size = XXH_ROWS[name]
+    batch = fsg.make_batch(fsg.KIND_TEXT, np.full(n, size, np.uint32))
+    H = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    s = torch.cuda.current_stream()
+    d_raw, d_ro, d_rl = H(batch.data), H(batch.offsets), H(batch.lens)
+    d_x = torch.zeros(n, dtype=torch.int32, device=dev)
+    m = alternate(torch, s, [lambda: codec.lz4f_xxh32(d_raw, d_ro, d_rl, n, d_x, stream=s)], warmup, launches)[0]
+    import lz4f_ref
+    got = d_x.cpu().numpy().view(np.uint32)
+    sample = [0, n - 1] if size > (1 << 20) else list(np.linspace(0, n - 1, 4).astype(np.int64))
+    ok = all(int(got[i]) == lz4f_ref.xxh32(batch.item(int(i))) for i in set(int(v) for v in sample))
+    print(json.dumps({"mode": "xxh", "row": name, "n": n, "size": size, "launches": launches, "warmup": warmup,
+                      "call": m, "gib_per_s": round(batch.total / 2**30 / (m["median_ms"] / 1e3), 2),
+                      "sample_equals_oracle": ok}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sums", action="store_true",
+                    help="sized frames without / with content / block / both checksums (rows as row[@id])")
+    ap.add_argument("--kinds", default="", help="--sums: a subset of none,content,block,both")
+    ap.add_argument("--decompress-only", action="store_true", help="--sums: compress once, untimed")
+    ap.add_argument("--xxh", action="store_true", help="fsg_lz4f_xxh32_batch alone (rows of XXH_ROWS)")
     ap.add_argument("--rows", default="16x4m,c3")
     ap.add_argument("--no-size", action="store_true", help="frames without a content size: serial against routed")
     ap.add_argument("--checksum", type=int, default=0, help="--no-size: frames with a content checksum")
@@ -406,6 +509,18 @@ def main():
     codec = fsg.SnappyGPU(0)
     if a.length_pass:
         length_pass(torch, codec, a.warmup, a.launches)
+        return
+    if a.xxh:
+        for name in ("1x4m,16x4m,1024x64k,c3" if a.rows == "16x4m,c3" else a.rows).split(","):
+            xxh_row(torch, codec, name, a.warmup, a.launches)
+            torch.cuda.empty_cache()
+        return
+    if a.sums:
+        for item in ("16x4m@4,16x4m@7" if a.rows == "16x4m,c3" else a.rows).split(","):
+            name, _, spec = item.partition("@")
+            sums_row(torch, codec, name, int(spec) if spec else a.bid, a.warmup, a.launches,
+                     only=a.kinds.split(",") if a.kinds else None, time_compress=not a.decompress_only)
+            torch.cuda.empty_cache()
         return
     if a.linked:
         rows = "16x4m@4,16x4m@7,4096x128k@4,1x128k@4" if a.rows == "16x4m,c3" else a.rows
