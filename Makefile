@@ -6,8 +6,8 @@ PKG      := flare-cpp_amd
 LIB      := $(PKG)/lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall
 CSRC     := $(PKG)/csrc/capi.hip $(PKG)/csrc/snappy_decode.hip $(PKG)/csrc/snappy_decode_v3.hip $(PKG)/csrc/snappy_decode_v4.hip $(PKG)/csrc/snappy_decode_partial.hip \
-            $(PKG)/csrc/snappy_encode.hip $(PKG)/csrc/snappy_encode_v3.hip $(PKG)/csrc/snappy_encode_wave.hip $(PKG)/csrc/gather.hip $(PKG)/csrc/pack.hip $(PKG)/csrc/lz4.hip $(PKG)/csrc/lz4_decode2.hip $(PKG)/csrc/lz4_encode_wave.hip $(PKG)/csrc/lz4_frame.hip
-CHDRS    := $(wildcard $(PKG)/csrc/*.h) include/flare_snappy_gpu.h include/flare_lz4_gpu.h
+            $(PKG)/csrc/snappy_encode.hip $(PKG)/csrc/snappy_encode_v3.hip $(PKG)/csrc/snappy_encode_wave.hip $(PKG)/csrc/gather.hip $(PKG)/csrc/pack.hip $(PKG)/csrc/lz4.hip $(PKG)/csrc/lz4_decode2.hip $(PKG)/csrc/lz4_encode_wave.hip $(PKG)/csrc/lz4_frame.hip $(PKG)/csrc/inflate.hip
+CHDRS    := $(wildcard $(PKG)/csrc/*.h) include/flare_snappy_gpu.h include/flare_lz4_gpu.h include/flare_deflate_gpu.h
 OBJDIR   := build/obj
 
 all: gpu host datagen oracle cpptests hostbench echobench
@@ -26,7 +26,7 @@ $(LIB)/libflare_snappy_gpu.so: $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/%.o,$(CSRC
 # handler + flat API): host-only code built with g++ against the HIP runtime.
 HOSTCXX   := g++ -std=c++17 -O2 -fPIC -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 HOST_SRC  := $(wildcard $(PKG)/host/*.cc)
-HOST_HDRS := $(wildcard $(PKG)/host/*.h) include/flare_snappy_gpu.h $(PKG)/csrc/lz4_frame_format.h
+HOST_HDRS := $(wildcard $(PKG)/host/*.h) include/flare_snappy_gpu.h $(PKG)/csrc/lz4_frame_format.h $(PKG)/csrc/inflate_format.h
 host: $(LIB)/libflare_rpc_snappy.so
 
 $(LIB)/libflare_rpc_snappy.so: $(HOST_SRC) $(HOST_HDRS) $(LIB)/libflare_snappy_gpu.so

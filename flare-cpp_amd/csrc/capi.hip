@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "../../include/flare_deflate_gpu.h"
 #include "../../include/flare_lz4_gpu.h"
 #include "../../include/flare_snappy_gpu.h"
 #include "launch.h"
@@ -682,6 +683,46 @@ int fsg_lz4f_content_sizes_batch(const uint8_t* d_in, const uint64_t* d_in_off, 
   return record(fsg::launch_lz4f_content_sizes(d_in, d_in_off, d_in_len, n_msgs, d_content_size, d_status,
                                                (hipStream_t)stream),
                 "fsg_lz4f_content_sizes_batch");
+}
+
+// ---- inflate (include/flare_deflate_gpu.h)
+int fsg_inflate_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_msgs,
+                      uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_cap, uint32_t* d_out_len,
+                      int32_t* d_status, uint32_t format, void* stream) {
+  if (format > FSG_INFLATE_GZIP) return FSG_ERR_INVALID_ARG;
+  if (n_msgs == 0) return FSG_SUCCESS;
+  if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status)
+    return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_inflate(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
+                                    d_status, format, (hipStream_t)stream),
+                "fsg_inflate_batch");
+}
+
+int fsg_inflate_lengths_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                              uint32_t n_msgs, uint64_t* d_length, int32_t* d_status, uint32_t format,
+                              void* stream) {
+  if (format > FSG_INFLATE_GZIP) return FSG_ERR_INVALID_ARG;
+  if (n_msgs == 0) return FSG_SUCCESS;
+  if (!d_in || !d_in_off || !d_in_len || !d_length || !d_status) return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_inflate_lengths(d_in, d_in_off, d_in_len, n_msgs, d_length, d_status, format,
+                                            (hipStream_t)stream),
+                "fsg_inflate_lengths_batch");
+}
+
+int fsg_crc32_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_msgs,
+                    uint32_t* d_crc, void* stream) {
+  if (n_msgs == 0) return FSG_SUCCESS;
+  if (!d_in || !d_in_off || !d_in_len || !d_crc) return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_inflate_sum(d_in, d_in_off, d_in_len, n_msgs, d_crc, false, (hipStream_t)stream),
+                "fsg_crc32_batch");
+}
+
+int fsg_adler32_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_msgs,
+                      uint32_t* d_adler, void* stream) {
+  if (n_msgs == 0) return FSG_SUCCESS;
+  if (!d_in || !d_in_off || !d_in_len || !d_adler) return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_inflate_sum(d_in, d_in_off, d_in_len, n_msgs, d_adler, true, (hipStream_t)stream),
+                "fsg_adler32_batch");
 }
 
 int fsg_lz4f_compress_report(const void* header_host_copy, uint32_t n_msgs, size_t workspace_bytes,

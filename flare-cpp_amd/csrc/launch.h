@@ -124,6 +124,15 @@ hipError_t launch_lz4f_decoded_lengths(const u8* in, const u64* in_off, const u3
 hipError_t launch_lz4f_content_sizes(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* sizes,
                                      i32* status, hipStream_t stream);
 
+// ---- inflate (inflate.hip; include/flare_deflate_gpu.h): a wave per body, no workspace
+hipError_t launch_inflate(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out, const u64* out_off,
+                          const u32* out_cap, u32* out_len, i32* status, u32 format, hipStream_t stream);
+hipError_t launch_inflate_lengths(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* lengths,
+                                  i32* status, u32 format, hipStream_t stream);
+// fsg_crc32_batch / fsg_adler32_batch: the checksum kernel alone
+hipError_t launch_inflate_sum(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u32* sum, bool adler,
+                              hipStream_t stream);
+
 // ---- path report (capi.hip: fsg_decompress_report and its kin): what each
 // codec's 256-byte workspace header holds after a call, read from a host copy
 struct DecodeHeaderCounts {

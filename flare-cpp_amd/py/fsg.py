@@ -17,7 +17,7 @@ PKG_DIR = Path(__file__).resolve().parents[1]
 LIB_DIR = PKG_DIR / "lib"
 REPO_DIR = PKG_DIR.parent
 HEADER = REPO_DIR / "include" / "flare_snappy_gpu.h"
-HEADERS = (HEADER, REPO_DIR / "include" / "flare_lz4_gpu.h")
+HEADERS = (HEADER, REPO_DIR / "include" / "flare_lz4_gpu.h", REPO_DIR / "include" / "flare_deflate_gpu.h")
 
 FSG_OK, FSG_CORRUPT, FSG_BAD_HEADER, FSG_SLOT_TOO_SMALL, FSG_IOV_TOO_SMALL = 0, 1, 2, 3, 4
 FSG_FLAG_VALIDATE_ONLY, FSG_FLAG_STRICT_HEADER = 1, 2
@@ -51,6 +51,8 @@ Lz4fDecodeReport = _report_struct("Lz4fDecodeReport", (
 LZ4F_NO_CONTENT_SIZE = 0xFFFFFFFFFFFFFFFF
 # fsg_lz4f_compress_batch_flags' flags (FSG_LZ4F_FLAG_*)
 LZ4F_FLAG_CONTENT_CHECKSUM, LZ4F_FLAG_BLOCK_CHECKSUMS, LZ4F_FLAG_NO_CONTENT_SIZE = 1, 2, 4
+# fsg_inflate_batch's formats (FSG_INFLATE_*, include/flare_deflate_gpu.h)
+INFLATE_RAW, INFLATE_ZLIB, INFLATE_GZIP = 0, 1, 2
 PATH_MAIN, PATH_SINGLE_DESIGN, PATH_NO_WORKSPACE, PATH_FORCED = 0, 1, 2, 3
 
 _SIGS = {
@@ -103,12 +105,16 @@ _SIGS = {
     "fsg_lz4f_decoded_lengths_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _sz, _vp]),
     "fsg_lz4f_compress_report": (_c.c_int, [_vp, _u32, _sz, _u32, _c.POINTER(Lz4fEncodeReport)]),
     "fsg_lz4f_decompress_report": (_c.c_int, [_vp, _u32, _sz, _c.POINTER(Lz4fDecodeReport)]),
+    "fsg_inflate_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "fsg_inflate_lengths_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp]),
+    "fsg_crc32_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp]),
+    "fsg_adler32_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp]),
 }
 
 
 def header_symbols(header: Path | None = None) -> list[str]:
-    """Every fsg_* function declared in include/flare_snappy_gpu.h and
-    include/flare_lz4_gpu.h (or in `header`)."""
+    """Every fsg_* function declared in include/flare_snappy_gpu.h,
+    include/flare_lz4_gpu.h and include/flare_deflate_gpu.h (or in `header`)."""
     import re
     text = "".join(h.read_text() for h in ((header,) if header else HEADERS))
     return sorted(set(re.findall(r"\b(fsg_[a-z0-9_]+)\s*\(", text)))
@@ -122,7 +128,8 @@ _OPTIONAL = {"fsg_decompress_batch_2s", "fsg_decompress_batch_partial", "fsg_dec
              "fsg_lz4f_max_frame_length", "fsg_lz4f_compress_workspace_bytes", "fsg_lz4f_compress_batch",
              "fsg_lz4f_decompress_workspace_bytes", "fsg_lz4f_decompress_batch", "fsg_lz4f_content_sizes_batch",
              "fsg_lz4f_compress_report", "fsg_lz4f_decompress_report", "fsg_lz4f_decoded_lengths_batch",
-             "fsg_lz4f_max_frame_length_flags", "fsg_lz4f_xxh32_batch", "fsg_lz4f_compress_batch_flags"}
+             "fsg_lz4f_max_frame_length_flags", "fsg_lz4f_xxh32_batch", "fsg_lz4f_compress_batch_flags",
+             "fsg_inflate_batch", "fsg_inflate_lengths_batch", "fsg_crc32_batch", "fsg_adler32_batch"}
 
 
 def load_gpu_lib(path: Path | None = None) -> ctypes.CDLL:
@@ -374,6 +381,31 @@ class SnappyGPU:
         r = Lz4fDecodeReport()
         self._check(self.lib.fsg_lz4f_decompress_report(head, n, nbytes, _c.byref(r)), "fsg_lz4f_decompress_report")
         return self._report_dict(r)
+
+    # ---- inflate (include/flare_deflate_gpu.h)
+    def inflate(self, d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len, d_status,
+                fmt=INFLATE_ZLIB, stream=None):
+        """fsg_inflate_batch: raw deflate, zlib or gzip bodies (INFLATE_*), no workspace."""
+        self._check(self.lib.fsg_inflate_batch(
+            _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_out), _ptr(d_out_off), _ptr(d_out_cap),
+            _ptr(d_out_len), _ptr(d_status), fmt, self._stream(stream)), "fsg_inflate_batch")
+
+    def inflate_lengths(self, d_in, d_in_off, d_in_len, n, d_length, d_status, fmt=INFLATE_ZLIB, stream=None):
+        """fsg_inflate_lengths_batch (d_length int64 / uint64): the exact
+        decoded lengths, no output written, the trailing checksum not judged."""
+        self._check(self.lib.fsg_inflate_lengths_batch(
+            _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_length), _ptr(d_status), fmt,
+            self._stream(stream)), "fsg_inflate_lengths_batch")
+
+    def crc32(self, d_in, d_in_off, d_in_len, n, d_crc, stream=None):
+        """fsg_crc32_batch: zlib.crc32 of each body into d_crc (int32 / uint32, n entries)."""
+        self._check(self.lib.fsg_crc32_batch(_ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_crc),
+                                             self._stream(stream)), "fsg_crc32_batch")
+
+    def adler32(self, d_in, d_in_off, d_in_len, n, d_adler, stream=None):
+        """fsg_adler32_batch: zlib.adler32 of each body into d_adler."""
+        self._check(self.lib.fsg_adler32_batch(_ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_adler),
+                                               self._stream(stream)), "fsg_adler32_batch")
 
     # ---- path reports (fsg_decompress_report and its kin)
     def _report_header(self, workspace):
