@@ -240,8 +240,8 @@ __attribute__((amdgpu_waves_per_eu(kLean ? 6 : 1))) void index_kernel(
   // plus the <= 3 an iteration spans.
   constexpr bool kSuper = !kPlanned && !kLean;
   constexpr u32 kBG = kLean ? 2 : (kSuper ? 8 : 4), kBW = 4 * kBG;
-  // per wave, [dword][lane]; dword 64 = copy of dword 0; 65..68 absorb
-  // unused prefetches
+  // per wave, [dword][lane]; dwords kRD + 1 .. kRD + 4 absorb unused
+  // prefetches (dword kRD is not used)
   // The lean form takes its LDS dynamically (idx_lean_lds_bytes(), given at
   // launch): with a compile-time size the compiler sizes the VGPR allocation
   // for the occupancy that LDS alone would allow (97 registers reserved for
@@ -256,29 +256,50 @@ __attribute__((amdgpu_waves_per_eu(kLean ? 6 : 1))) void index_kernel(
   u32* const bmr = kLean ? idx_dyn_lds + kW * (kRD + 5) * kWave + 256 + wv * kBW * kWave : bmr_s[wv];
 
   const u32 lane = threadIdx.x & 63;
-  // Tag table (the role of char_table, snappy.cc:516-549): per tag byte c,
-  // bits 0-4 the right shift of 0xffffffff that masks the nb extra bytes
-  // ((32 - 8 nb) & 31: a shift uses the low 5 bits of its operand), 5 long
-  // literal, 8-15 advance without a long literal's length, 16-23 length
-  // (short literal / copies).
+  // The unrolled walk addresses both rings from the workgroup's first wave, so
+  // the array's LDS address folds into the instruction and the wave's share
+  // into one per-lane term: ring byte P of this lane is
+  // ring_b0[(dword << 8) + ((P & 3) | ring_lane)], bit word w is
+  // bmr_w0[(w << 6) + bmr_lane].
+  constexpr u32 kRDlog = kLean ? 5 : 6, kBWlog = kLean ? 3 : (kSuper ? 5 : 4);
+  static_assert(kRD == 1u << kRDlog && kBW == 1u << kBWlog, "ring sizes are powers of two");
+  const u8* const ring_b0 = reinterpret_cast<const u8*>(kLean ? idx_dyn_lds : &ring_s[0][0]);
+  u32* const bmr_w0 = kLean ? idx_dyn_lds + kW * (kRD + 5) * kWave + 256 : &bmr_s[0][0];
+  const u32 ring_lane = (wv * (kRD + 5) * kWave + lane) * 4, bmr_lane = wv * kBW * kWave + lane;
+  // Tag table (the role of char_table, snappy.cc:516-549): per tag byte c one
+  // word that a single add applies to the walk's packed accumulator: bits
+  // 16-31 the output length (<= kMaxLen), bits 6-15 the advance (tag byte +
+  // extra bytes + a short literal's bytes, <= kMaxAdv), bits 0-5 zero.  The
+  // advance sits at bit 6 so that the accumulator's position field, masked,
+  // IS the ring address of its dword ([dword][lane]: byte P of a lane is at
+  // (P >> 2) * 256 + lane * 4 + (P & 3), and ((P << 6) & 0x3f00) is the first
+  // term).  The four long literal tags (0xF0, 0xF4, 0xF8, 0xFC) hold 0, which
+  // is also their flag: the unrolled walk stays on such a tag and the
+  // long-literal path after it takes its length from the ring.  Every other
+  // entry is non-zero.
+  constexpr u32 kMaxAdv = 65, kMaxLen = 64, kPosShift = 6;
+  // The position field starts an iteration at the low 8 bits of the ring
+  // position and advances by at most kMaxDist (the clamp of the limit) plus
+  // one tag: it stays inside bits 6-15, so no carry reaches the length, and
+  // the length half holds an iteration's sum.
+  constexpr u32 kMaxDist = 255;
+  static_assert(255 + kMaxDist + kMaxAdv < (1u << (16 - kPosShift)), "position field of the packed accumulator overflows");
+  static_assert(kIdxTags * kMaxLen <= 0xffffu, "length half of the packed accumulator overflows");
 #pragma unroll
   for (u32 q = 0; q < 4 / kW; ++q) {
     const u32 c = threadIdx.x * (4 / kW) + q, type = c & 3, l0 = (c >> 2) + 1;
-    u32 nb, len, lit = 0, ll = 0;
+    u32 adv, len;
     if (type == 0) {
-      lit = 1;
-      nb = l0 > 60 ? l0 - 60 : 0;
-      ll = nb ? 1 : 0;
-      len = nb ? 0 : l0;
+      len = l0 > 60 ? 0 : l0;
+      adv = l0 > 60 ? 0 : 1 + l0;
     } else if (type == 1) {
-      nb = 1;
+      adv = 2;
       len = 4 + ((c >> 2) & 7);
     } else {
-      nb = type == 2 ? 2 : 4;
+      adv = type == 2 ? 3 : 5;
       len = l0;
     }
-    const u32 adv = 1 + nb + (lit && !ll ? len : 0);
-    tagtab[c] = ((32 - 8 * nb) & 31) | (ll << 5) | (adv << 8) | (len << 16);
+    tagtab[c] = (len << 16) | (adv << kPosShift);
   }
   __syncthreads();
   // planned with a walk order: lane g walks message walk_perm[g], the
@@ -330,7 +351,6 @@ __attribute__((amdgpu_waves_per_eu(kLean ? 6 : 1))) void index_kernel(
     const u32 d = live ? (k & (kRC - 1)) * 4 : kRD + 1;
 #pragma unroll
     for (int i = 0; i < 4; ++i) ring[(d + i) * kWave + lane] = v[i];
-    ring[(d == 0 ? kRD : kRD + 1) * kWave + lane] = v[0];
   };
   // Single-literal message (random bodies: the encoder emits one literal when
   // it finds no match): its first tag is a literal whose bytes end the input.
@@ -390,59 +410,83 @@ __attribute__((amdgpu_waves_per_eu(kLean ? 6 : 1))) void index_kernel(
       const u32 ring_end = 16 * wend >= 4 + ibal ? 16 * wend - 4 - ibal : 0u;
       lim = (wend > last_chunk || ring_end > n_in) ? n_in : ring_end;
     }
-    // Software-pipelined: tag j+1's ring read is issued (in program order)
-    // before tag j's checks and its ds_or, so the LDS latency overlaps them;
-    // the compiler does not move LDS reads above the atomic.
-    auto ring_read = [&](u32 at, u32& lo, u32& hi) {
-      const u32 P = at + ibal;
-      const u32 dw = (P >> 2) & (kRD - 1);
-      lo = ring[dw * kWave + lane];
-      hi = ring[(dw + 1) * kWave + lane];
-    };
-    u32 lo, hi;
-    ring_read(ip, lo, hi);
+    // The unrolled walk keeps one packed accumulator per iteration, in the
+    // tag table's format: output length of the iteration so far in bits
+    // 16-31, ring position in bits 6-15 (the low 8 bits of ip + ibal at the
+    // iteration's start, plus the advance since; the static_asserts at the
+    // table bound both fields).  A tag costs one byte read of the ring, one
+    // table read and one add; the walk never looks at a copy's offset bytes.
+    // The 16-bit compare `pos < lim_pos` is `ip < lim`.  The limit's distance
+    // is clamped to kMaxDist: the ring holds no more than 256 bytes from the
+    // start, and a tag the clamp cuts off waits for the next iteration.
     const u32 op_it = op;
-    u32 lmax = 0;  // the largest long-literal length looked at this iteration
+    const u32 pos_it = (ip + ibal) & 255u;
+    const u32 ip_base = ip - pos_it;  // ip = ip_base + position field (mod 2^32)
+    const u32 dist = lim > ip ? lim - ip : 0u;
+    const u16 lim_pos = (u16)((pos_it + (dist < kMaxDist ? dist : kMaxDist)) << kPosShift);
+    auto tag_read = [&](u32 a) -> u32 {
+      return ring_b0[(a & ((kRD - 1) << 8)) + (__builtin_amdgcn_ubfe(a, kPosShift, 2) | ring_lane)];
+    };
+    // Software-pipelined: tag j+1's ring read is issued (in program order)
+    // before tag j's ds_or, so the LDS latency overlaps it; the compiler does
+    // not move LDS reads above the atomic.  The read after the last tag shows
+    // the long-literal path what the lane stands on.
+    u32 acc = pos_it << kPosShift;
+    u32 c = tag_read(acc);
 #pragma unroll
     for (int j = 0; j < kIdxTags; ++j) {
-      const u32 bsh = (ip + ibal) & 3;
-      const u32 t0 = alignbyte(hi, lo, bsh);          // bytes ip..ip+3
-      const u32 ext = alignbyte(hi >> (8 * bsh), t0, 1);  // bytes ip+1..ip+4
-      // tag decode through the tag table (DecompressAllTags :716-787): the
-      // 0..4 bytes after the tag byte are a literal's length or a copy's
-      // offset, masked to their count nb; selects, no exec-mask branches.
-      const u32 c = t0 & 0xffu;
+      // The walk advances over every tag below lim whether or not it will
+      // pass the iteration's checks, so they stay off the dependency chain.
+      // A long literal's entry is 0: the lane stays on it, looks at it again
+      // in every remaining slot and ORs the same bit again.
       const u32 e = tagtab[c];
-      const u32 val = ext & (0xffffffffu >> (e & 31u));
-      // a long literal's length (uint32 wrap: 0xffffffff+1 == 0, as the
-      // reference's uint32 sum), else the table's (0 for long literals); masks,
-      // not a select, so the compiler keeps the unrolled walk branch-free
-      const u32 llmask = 0u - ((e >> 5) & 1u);
-      const u32 lpart = (val + 1u) & llmask;
-      const u32 len = lpart + ((e >> 16) & 0xffu);
-      // The walk advances over every tag below lim whether or not it passed
-      // its checks, so the checks stay off the ip -> ip dependency chain.
-      // After the first failing tag the status is final (kCorrupt): what the
-      // walk reads from there on only sets bits in the LDS ring, which are
-      // never stored for a corrupt message, and ring indices are masked.
-      const bool look = ip < lim;
-      const u32 adv = (e >> 8) & 0xffu;  // tag byte + extra bytes (+ a short literal's bytes)
-      const u32 step = adv + lpart;
-      const u32 ip_next = look ? ip + step : ip;
-      if (j + 1 < kIdxTags) ring_read(ip_next, lo, hi);
-      // Bounds are checked once per iteration (below), not per tag (~5 fewer
-      // VALU per tag step): a tag whose bytes run past the input leaves
-      // ip_next > n_in (no u32 wrap while lpart <= n_in, since ip <= n_in < 2^31 and adv <= 65), after
-      // which no later tag of the iteration is looked at (ip >= lim); a
-      // larger lpart (a huge or wrapping 4-byte literal length) shows in lmax.
-      // The bit and length of such a tag land only in state that a corrupt
-      // message never stores.
-      lmax = look && lpart > lmax ? lpart : lmax;
-      atomicOr(&bmr[((ip >> 5) & (kBW - 1)) * kWave + lane], look ? 1u << (ip & 31) : 0u);
-      op += look ? len : 0u;
-      ip = ip_next;
+      const bool look = (u16)acc < lim_pos;
+      const u32 acc_next = acc + (look ? e : 0u);
+      c = tag_read(acc_next);
+      const u32 at = ip_base + __builtin_amdgcn_ubfe(acc, kPosShift, 16 - kPosShift);
+      atomicOr(&bmr_w0[(__builtin_amdgcn_ubfe(at, 5, kBWlog) << 6) + bmr_lane], look ? 1u << (at & 31) : 0u);
+      acc = acc_next;
     }
-    if (status < 0 && (ip > n_in || lmax > n_in)) status = kCorrupt;
+    ip = ip_base + __builtin_amdgcn_ubfe(acc, kPosShift, 16 - kPosShift);
+    op = op_it + (acc >> 16);
+
+    // ---------- long literals (tags 0xF0/0xF4/0xF8/0xFC), off the unrolled
+    // walk: a wave-uniform branch for the lanes that stand on one below lim.
+    // A lane stays here while its next tag is a long literal too, so a body
+    // of long literals does not take one iteration per tag; a literal that
+    // leaves the ring (ip >= lim) ends the lane's iteration.
+    // Bounds are checked once per iteration (below): a tag whose bytes run
+    // past the input leaves ip > n_in (no u32 wrap while the length is
+    // <= n_in, since ip <= n_in < 2^31), after which the lane looks at
+    // nothing more (ip >= lim); a larger length (a huge or wrapping 4-byte
+    // one, which could bring ip back below lim) stops the lane and shows in
+    // ll_bad.  The bit and length of such a tag land only in state that a
+    // corrupt message never stores, and ring indices are masked.
+    bool ll_bad = false;
+    bool ll = ip < lim && (c & 0xf3u) == 0xf0u;
+    while (__any(ll)) {
+      const u32 P = ip + ibal;
+      const u32 dw = (P >> 2) & (kRD - 1);
+      const u32 lo = ring[dw * kWave + lane];
+      const u32 hi = ring[((dw + 1) & (kRD - 1)) * kWave + lane];
+      const u32 bsh = P & 3;
+      const u32 t0 = alignbyte(hi, lo, bsh);              // bytes ip..ip+3
+      const u32 ext = alignbyte(hi >> (8 * bsh), t0, 1);  // bytes ip+1..ip+4
+      const u32 cc = t0 & 0xffu;
+      ll = ll && (cc & 0xf3u) == 0xf0u;
+      if (ll) {
+        // the length's nb = 1..4 bytes follow the tag byte; uint32 wrap
+        // (0xffffffff + 1 == 0) as the reference's uint32 sum
+        const u32 nb = (cc >> 2) - 59u;
+        const u32 lpart = (ext & (0xffffffffu >> (32 - 8 * nb))) + 1u;
+        atomicOr(&bmr[((ip >> 5) & (kBW - 1)) * kWave + lane], 1u << (ip & 31));
+        ll_bad = lpart > n_in;
+        ip += 1 + nb + lpart;
+        op += lpart;
+        ll = !ll_bad && ip < lim;
+      }
+    }
+    if (status < 0 && (ip > n_in || ll_bad)) status = kCorrupt;
     // writer space (:1166, :1400), checked once per iteration: op only grows,
     // and one iteration cannot wrap it (accepted literals fit the input)
     if (status < 0 && (op > expected || op < op_it)) status = kCorrupt;
