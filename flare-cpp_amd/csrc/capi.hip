@@ -9,6 +9,7 @@
 #include "../../include/flare_deflate_gpu.h"
 #include "../../include/flare_lz4_gpu.h"
 #include "../../include/flare_snappy_gpu.h"
+#include "deflate_format.h"
 #include "launch.h"
 #include "launch_util.h"
 #include "options.h"
@@ -723,6 +724,43 @@ int fsg_adler32_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint3
   if (!d_in || !d_in_off || !d_in_len || !d_adler) return FSG_ERR_INVALID_ARG;
   return record(fsg::launch_inflate_sum(d_in, d_in_off, d_in_len, n_msgs, d_adler, true, (hipStream_t)stream),
                 "fsg_adler32_batch");
+}
+
+// ---- deflate compress (include/flare_deflate_compress_gpu.h)
+size_t fsg_deflate_max_length(size_t n, uint32_t format) { return (size_t)defl::max_length(n, format); }
+
+size_t fsg_deflate_workspace_bytes(uint32_t n_msgs, uint64_t total_in_bytes) {
+  return fsg::deflate_workspace_bytes(n_msgs, total_in_bytes);
+}
+
+int fsg_deflate_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_msgs,
+                      uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status,
+                      uint32_t format, void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (format > FSG_DEFLATE_GZIP) return FSG_ERR_INVALID_ARG;
+  if (n_msgs == 0) return FSG_SUCCESS;
+  if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len || !d_status || !d_workspace)
+    return FSG_ERR_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(d_workspace) & 15u) return FSG_ERR_INVALID_ARG;
+  if (fsg::deflate_unit_capacity(n_msgs, workspace_bytes) == 0) return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_deflate(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_len, d_status, format,
+                                    d_workspace, workspace_bytes, (hipStream_t)stream),
+                "fsg_deflate_batch");
+}
+
+int fsg_deflate_report(const void* header_host_copy, uint32_t n_msgs, size_t workspace_bytes,
+                       struct fsg_deflate_report* out) {
+  if (!header_host_copy || !out) return FSG_ERR_INVALID_ARG;
+  const uint64_t cap = fsg::deflate_unit_capacity(n_msgs, workspace_bytes);
+  if (n_msgs && cap == 0) return FSG_ERR_INVALID_ARG;
+  fsg::DeflateHeaderCounts c;
+  fsg::deflate_header_counts(header_host_copy, &c);
+  out->units = c.units;
+  out->stored_units = c.stored;
+  out->fixed_units = c.fixed;
+  out->dynamic_units = c.dynamic;
+  out->overflow_messages = c.overflow;
+  out->unit_entries = cap;
+  return FSG_SUCCESS;
 }
 
 int fsg_lz4f_compress_report(const void* header_host_copy, uint32_t n_msgs, size_t workspace_bytes,

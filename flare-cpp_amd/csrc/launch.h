@@ -133,6 +133,18 @@ hipError_t launch_inflate_lengths(const u8* in, const u64* in_off, const u32* in
 hipError_t launch_inflate_sum(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u32* sum, bool adler,
                               hipStream_t stream);
 
+// ---- deflate compress (deflate.hip; include/flare_deflate_compress_gpu.h).  The
+// call gets no input size: deflate_unit_capacity gives the units a workspace
+// holds (0: below deflate_workspace_bytes(n_msgs, 0)).
+size_t deflate_workspace_bytes(u32 n_msgs, u64 total_in_bytes);
+u64 deflate_unit_capacity(u32 n_msgs, size_t ws_bytes);
+hipError_t launch_deflate(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out, const u64* out_off,
+                          u32* out_len, i32* status, u32 format, void* ws, size_t ws_bytes, hipStream_t stream);
+struct DeflateHeaderCounts {
+  u32 units, stored, fixed, dynamic, overflow;
+};
+void deflate_header_counts(const void* header, DeflateHeaderCounts* c);
+
 // ---- path report (capi.hip: fsg_decompress_report and its kin): what each
 // codec's 256-byte workspace header holds after a call, read from a host copy
 struct DecodeHeaderCounts {

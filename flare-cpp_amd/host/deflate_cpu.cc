@@ -1,0 +1,169 @@
+// deflate_cpu.cc -- see deflate_cpu.h.  A serial reading of
+// csrc/deflate_format.h: every rule is a function of that header called with
+// (lane, nlanes) = (0, 1); what is written here is only the order of the
+// steps, which csrc/deflate.hip follows phase by phase.
+#include "deflate_cpu.h"
+
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../csrc/deflate_format.h"
+#include "inflate_cpu.h"
+
+namespace {
+
+using namespace defl;
+
+struct UnitReader {
+  const uint8_t* p;
+  uint32_t n;
+  uint32_t load32(uint32_t q) const {
+    uint32_t v = 0;
+    if (q + 4 <= n) {
+      memcpy(&v, p + q, 4);
+      return v;
+    }
+    for (uint32_t i = 0; i < 4 && q + i < n; ++i) v |= (uint32_t)p[q + i] << (8 * i);
+    return v;
+  }
+};
+
+struct Scratch {
+  uint16_t table[kTableEntries];
+  Build b;
+  std::vector<uint32_t> tokens, win;
+};
+
+// Phase 1: the window parse.  Tokens (the end-of-block token last) and symbol counts.
+void parse_unit(const UnitReader& rd, Scratch& s) {
+  for (uint32_t i = 0; i < kTableEntries; ++i) s.table[i] = (uint16_t)kNoPos;
+  memset(&s.b, 0, sizeof s.b);
+  s.tokens.clear();
+  const uint32_t n = rd.n;
+  uint32_t entry = 0;
+  for (uint32_t base = 0; base < n; base += kWindow) {
+    const uint32_t cnt = n - base < kWindow ? n - base : kWindow;
+    uint32_t rec[kWindow];
+    for (uint32_t i = 0; i < cnt; ++i) rec[i] = token_at(rd, n, base + i, s.table);
+    uint32_t cur = entry;
+    while (cur < cnt) {
+      s.tokens.push_back(rec[cur]);
+      count_token(&s.b, rec[cur]);
+      cur += tok_advance(rec[cur]);
+    }
+    entry = cur - cnt;  // 0 in the last window: no token passes the unit's end
+    for (uint32_t i = 0; i < cnt; ++i)
+      if (n - (base + i) >= kMinMatch) s.table[hash4(rd.load32(base + i))] = (uint16_t)(base + i);
+  }
+  s.tokens.push_back(kTokEnd);
+  count_token(&s.b, kTokEnd);
+}
+
+// Phases 2 and 3 for one unit; its bytes are appended to out.
+uint32_t compress_unit(const uint8_t* in, uint32_t n, bool last, Scratch& s, std::vector<uint8_t>* out) {
+  const UnitReader rd{in, n};
+  parse_unit(rd, s);
+  Build* b = &s.b;
+  build_lengths(b->hist, kLitSyms, 15, b->len, b, 0, 1);
+  build_lengths(b->hist + kDistBase, kDistSyms, 15, b->len + kDistBase, b, 0, 1);
+  const uint32_t header = build_dynamic_header(b, 0, 1);
+  uint32_t dyn, fix;
+  symbol_bits(b, 0, 1, &dyn, &fix);
+  const Choice c = choose_block(n, last, dyn + header, fix);
+  if (!out) return c.type;
+  if (c.type == kStored) {
+    uint8_t h[5];
+    write_stored_head(n, last, h);
+    out->insert(out->end(), h, h + 5);
+    out->insert(out->end(), in, in + n);
+    return c.type;
+  }
+  if (c.type == kFixed) {
+    fill_fixed_lengths(b, 0, 1);
+    assign_codes(b->len, infl::kFixedLens, b->code, b, 0, 1);
+    assign_codes(b->len + kDistBase, infl::kFixedDists, b->code + kDistBase, b, 0, 1);
+  } else {
+    assign_codes(b->len, kLitSyms, b->code, b, 0, 1);
+    assign_codes(b->len + kDistBase, kDistSyms, b->code + kDistBase, b, 0, 1);
+  }
+  s.win.assign(c.bytes / 4 + 4, 0);
+  uint32_t pos = write_block_header(b, c.type, last, s.win.data());
+  for (const uint32_t t : s.tokens) {
+    uint32_t nb;
+    const uint64_t v = token_bits(b, t, &nb);
+    put_bits(s.win.data(), pos, v, nb);
+    pos += nb;
+  }
+  const uint32_t bytes = write_block_tail(last, pos, s.win.data());
+  if (bytes != c.bytes) abort();  // the size formulas and the writer disagree
+  const uint8_t* w = reinterpret_cast<const uint8_t*>(s.win.data());
+  out->insert(out->end(), w, w + bytes);
+  return c.type;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t fsh_cpu_deflate_bound(size_t n, uint32_t format) { return (size_t)defl::max_length(n, format); }
+
+int fsh_cpu_deflate(uint32_t format, const void* in_, size_t n, void* out_, size_t cap, uint64_t* len) {
+  *len = 0;
+  if (format > kGzip) return infl::kStCorrupt;
+  const uint8_t* in = static_cast<const uint8_t*>(in_);
+  std::vector<uint8_t> body(wrapper_head(format));
+  write_wrapper_head(format, body.data());
+  std::vector<Scratch> scratch(1);
+  const uint64_t units = unit_count(n);
+  for (uint64_t u = 0; u < units; ++u) {
+    const uint64_t first = u * kUnit;
+    const uint32_t un = (uint32_t)(n - first < kUnit ? n - first : kUnit);
+    compress_unit(in + first, un, u + 1 == units, scratch[0], &body);
+  }
+  uint8_t tail[8];
+  const uint32_t sum = format == kZlib ? fsh_cpu_adler32(in, n) : format == kGzip ? fsh_cpu_crc32(in, n) : 0u;
+  write_wrapper_tail(format, sum, (uint32_t)n, tail);
+  body.insert(body.end(), tail, tail + wrapper_tail(format));
+  if (body.size() > cap) return infl::kStSlotTooSmall;
+  if (!body.empty()) memcpy(out_, body.data(), body.size());
+  *len = body.size();
+  return infl::kStOk;
+}
+
+void fsh_cpu_deflate_unit_types(const void* in_, size_t n, uint64_t counts[3]) {
+  const uint8_t* in = static_cast<const uint8_t*>(in_);
+  std::vector<Scratch> scratch(1);
+  const uint64_t units = unit_count(n);
+  for (uint64_t u = 0; u < units; ++u) {
+    const uint64_t first = u * kUnit;
+    const uint32_t un = (uint32_t)(n - first < kUnit ? n - first : kUnit);
+    ++counts[compress_unit(in + first, un, u + 1 == units, scratch[0], nullptr)];
+  }
+}
+
+size_t fsh_cpu_deflate_tokens(const void* in_, size_t n, uint32_t* tokens, size_t cap) {
+  if (n > kUnit) return 0;
+  std::vector<Scratch> scratch(1);
+  parse_unit(UnitReader{static_cast<const uint8_t*>(in_), (uint32_t)n}, scratch[0]);
+  const size_t cnt = scratch[0].tokens.size() - 1;
+  if (cnt > cap) return 0;
+  if (cnt) memcpy(tokens, scratch[0].tokens.data(), cnt * 4);
+  return cnt;
+}
+
+uint64_t fsh_cpu_deflate_limited(const void* in_, size_t n) {
+  const uint8_t* in = static_cast<const uint8_t*>(in_);
+  std::vector<Scratch> scratch(1);
+  uint64_t limited = 0;
+  const uint64_t units = unit_count(n);
+  for (uint64_t u = 0; u < units; ++u) {
+    const uint64_t first = u * kUnit;
+    const uint32_t un = (uint32_t)(n - first < kUnit ? n - first : kUnit);
+    compress_unit(in + first, un, u + 1 == units, scratch[0], nullptr);
+    limited += scratch[0].b.limited;
+  }
+  return limited;
+}
+
+}  // extern "C"

@@ -1,0 +1,44 @@
+// deflate_cpu.h -- the serial deflate writer over csrc/deflate_format.h: the
+// DEFINITION of the bytes fsg_deflate_batch produces
+// (include/flare_deflate_compress_gpu.h), and the host codec behind the gzip
+// and zlib compress handlers (gzip_compress.h).  No libz.  The streams are
+// legal raw deflate / zlib / gzip bodies that any inflate reads; they are not
+// the bytes zlib's deflate would write for the same input.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* n + 5 * max(1, ceil(n / 65472)) + 0, 6 or 18 wrapper bytes; 0 for an
+ * unknown format.  format: FSG_INFLATE_RAW / _ZLIB / _GZIP (0, 1, 2). */
+size_t fsh_cpu_deflate_bound(size_t n, uint32_t format);
+
+/* Compresses in[0 .. n) into out[0 .. cap).  Returns 0 (FSG_OK) with *len =
+ * the body's length, which never exceeds the bound.  Returns 3
+ * (FSG_SLOT_TOO_SMALL) when the body is longer than cap, and 1 (FSG_CORRUPT)
+ * for an unknown format; *len is 0 then and out is not written.  Bytes of out
+ * at and past *len are never written.  gzip's ISIZE is n mod 2^32. */
+int fsh_cpu_deflate(uint32_t format, const void *in, size_t n, void *out, size_t cap, uint64_t *len);
+
+/* The block types of the units the last-named call would choose, for tests
+ * and reports: counts[0..3) += stored, fixed, dynamic units of in[0 .. n). */
+void fsh_cpu_deflate_unit_types(const void *in, size_t n, uint64_t counts[3]);
+
+/* The parse of ONE unit (n <= 65472), for tests: its tokens without the end
+ * token into tokens[0 .. cap), the count returned (0 when n is too large or
+ * cap too small).  A literal is 0x80000000 | byte, a match length |
+ * distance << 9. */
+size_t fsh_cpu_deflate_tokens(const void *in, size_t n, uint32_t *tokens, size_t cap);
+
+/* How many of the literal/length and distance code sets built for
+ * in[0 .. n) (two per unit) were deeper than 15 bits and went through the
+ * length limiter. */
+uint64_t fsh_cpu_deflate_limited(const void *in, size_t n);
+
+#ifdef __cplusplus
+}
+#endif

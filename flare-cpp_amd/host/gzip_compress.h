@@ -1,0 +1,39 @@
+// gzip_compress.h -- CompressHandlers for COMPRESS_TYPE_GZIP (2) and
+// COMPRESS_TYPE_ZLIB (3), shaped like the reference's (flare
+// rpc/policy/gzip_compress.h: GzipCompress / GzipDecompress / ZlibCompress /
+// ZlibDecompress, same meaning of arguments and return values), written
+// against those signatures only.  The reference's optional third argument, a
+// GzipCompressOptions* with a level and a format, is not taken: there is one
+// level, and the format is the function's.
+//
+// Compress writes the bodies csrc/deflate_format.h defines (host/deflate_cpu.h:
+// legal gzip / zlib streams that any inflate reads, not zlib's bytes);
+// Decompress reads whatever zlib's inflate reads
+// (include/flare_deflate_gpu.h, "Acceptance rule"), one gzip member per body.
+// Per call the host codec runs: one body is one serial walk, which a CPU core
+// runs faster than one GPU wave.  Batches go through fsg_deflate_batch and
+// fsg_inflate_batch.
+#pragma once
+
+#include "compress.h"
+#include "cord_buf.h"
+
+namespace flare::rpc::policy {
+
+bool GzipCompress(const Message& msg, cord_buf* buf);
+bool GzipDecompress(const cord_buf& data, Message* msg);
+bool GzipCompress(const cord_buf& in, cord_buf* out);
+bool GzipDecompress(const cord_buf& in, cord_buf* out);
+
+bool ZlibCompress(const Message& msg, cord_buf* buf);
+bool ZlibDecompress(const cord_buf& data, Message* msg);
+bool ZlibCompress(const cord_buf& in, cord_buf* out);
+bool ZlibDecompress(const cord_buf& in, cord_buf* out);
+
+}  // namespace flare::rpc::policy
+
+namespace flare::rpc {
+// Registers the two handlers at COMPRESS_TYPE_GZIP and COMPRESS_TYPE_ZLIB once
+// per process; 0 when both registrations succeeded.
+int GlobalInitializeGzipZlib();
+}  // namespace flare::rpc

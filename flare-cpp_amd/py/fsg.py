@@ -17,7 +17,8 @@ PKG_DIR = Path(__file__).resolve().parents[1]
 LIB_DIR = PKG_DIR / "lib"
 REPO_DIR = PKG_DIR.parent
 HEADER = REPO_DIR / "include" / "flare_snappy_gpu.h"
-HEADERS = (HEADER, REPO_DIR / "include" / "flare_lz4_gpu.h", REPO_DIR / "include" / "flare_deflate_gpu.h")
+HEADERS = (HEADER, REPO_DIR / "include" / "flare_lz4_gpu.h", REPO_DIR / "include" / "flare_deflate_gpu.h",
+           REPO_DIR / "include" / "flare_deflate_compress_gpu.h")
 
 FSG_OK, FSG_CORRUPT, FSG_BAD_HEADER, FSG_SLOT_TOO_SMALL, FSG_IOV_TOO_SMALL = 0, 1, 2, 3, 4
 FSG_FLAG_VALIDATE_ONLY, FSG_FLAG_STRICT_HEADER = 1, 2
@@ -51,7 +52,10 @@ Lz4fDecodeReport = _report_struct("Lz4fDecodeReport", (
 LZ4F_NO_CONTENT_SIZE = 0xFFFFFFFFFFFFFFFF
 # fsg_lz4f_compress_batch_flags' flags (FSG_LZ4F_FLAG_*)
 LZ4F_FLAG_CONTENT_CHECKSUM, LZ4F_FLAG_BLOCK_CHECKSUMS, LZ4F_FLAG_NO_CONTENT_SIZE = 1, 2, 4
-# fsg_inflate_batch's formats (FSG_INFLATE_*, include/flare_deflate_gpu.h)
+# struct fsg_deflate_report (include/flare_deflate_compress_gpu.h)
+DeflateReport = _report_struct("DeflateReport", (
+    "units", "stored_units", "fixed_units", "dynamic_units", "overflow_messages", "unit_entries"))
+# fsg_inflate_batch's and fsg_deflate_batch's formats (FSG_INFLATE_* = FSG_DEFLATE_*, include/flare_deflate_gpu.h)
 INFLATE_RAW, INFLATE_ZLIB, INFLATE_GZIP = 0, 1, 2
 PATH_MAIN, PATH_SINGLE_DESIGN, PATH_NO_WORKSPACE, PATH_FORCED = 0, 1, 2, 3
 
@@ -109,6 +113,10 @@ _SIGS = {
     "fsg_inflate_lengths_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp]),
     "fsg_crc32_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp]),
     "fsg_adler32_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp]),
+    "fsg_deflate_max_length": (_sz, [_sz, _u32]),
+    "fsg_deflate_workspace_bytes": (_sz, [_u32, _u64]),
+    "fsg_deflate_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp]),
+    "fsg_deflate_report": (_c.c_int, [_vp, _u32, _sz, _c.POINTER(DeflateReport)]),
 }
 
 
@@ -129,7 +137,8 @@ _OPTIONAL = {"fsg_decompress_batch_2s", "fsg_decompress_batch_partial", "fsg_dec
              "fsg_lz4f_decompress_workspace_bytes", "fsg_lz4f_decompress_batch", "fsg_lz4f_content_sizes_batch",
              "fsg_lz4f_compress_report", "fsg_lz4f_decompress_report", "fsg_lz4f_decoded_lengths_batch",
              "fsg_lz4f_max_frame_length_flags", "fsg_lz4f_xxh32_batch", "fsg_lz4f_compress_batch_flags",
-             "fsg_inflate_batch", "fsg_inflate_lengths_batch", "fsg_crc32_batch", "fsg_adler32_batch"}
+             "fsg_inflate_batch", "fsg_inflate_lengths_batch", "fsg_crc32_batch", "fsg_adler32_batch",
+             "fsg_deflate_max_length", "fsg_deflate_workspace_bytes", "fsg_deflate_batch", "fsg_deflate_report"}
 
 
 def load_gpu_lib(path: Path | None = None) -> ctypes.CDLL:
@@ -406,6 +415,33 @@ class SnappyGPU:
         """fsg_adler32_batch: zlib.adler32 of each body into d_adler."""
         self._check(self.lib.fsg_adler32_batch(_ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_adler),
                                                self._stream(stream)), "fsg_adler32_batch")
+
+    # ---- deflate compress (include/flare_deflate_compress_gpu.h)
+    def deflate_max_length(self, n, fmt=INFLATE_ZLIB) -> int:
+        return self.lib.fsg_deflate_max_length(n, fmt)
+
+    def deflate_workspace_bytes(self, n, total_in_bytes) -> int:
+        return self.lib.fsg_deflate_workspace_bytes(n, total_in_bytes)
+
+    def deflate_workspace(self, n, total_in_bytes, device=None):
+        import torch
+        nbytes = self.deflate_workspace_bytes(n, total_in_bytes)
+        return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device or f"cuda:{self.device}")
+
+    def deflate(self, d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_len, d_status, workspace,
+                fmt=INFLATE_ZLIB, stream=None):
+        """fsg_deflate_batch: raw deflate, zlib or gzip bodies (INFLATE_*) into
+        slots of deflate_max_length(len, fmt) bytes."""
+        ws = 0 if workspace is None else workspace.numel() * workspace.element_size()
+        self._check(self.lib.fsg_deflate_batch(
+            _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len),
+            _ptr(d_status), fmt, _ptr(workspace), ws, self._stream(stream)), "fsg_deflate_batch")
+
+    def deflate_report(self, workspace, n) -> dict:
+        head, nbytes = self._report_header(workspace)
+        r = DeflateReport()
+        self._check(self.lib.fsg_deflate_report(head, n, nbytes, _c.byref(r)), "fsg_deflate_report")
+        return self._report_dict(r)
 
     # ---- path reports (fsg_decompress_report and its kin)
     def _report_header(self, workspace):

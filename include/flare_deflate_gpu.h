@@ -1,9 +1,12 @@
 /*
- * flare_deflate_gpu.h -- batched inflate on MI355X (gfx950), in
+ * flare_deflate_gpu.h -- batched inflate and deflate on MI355X (gfx950), in
  * libflare_snappy_gpu.so next to the Snappy and LZ4 calls
  * (include/flare_snappy_gpu.h: same batch layout, same status words, same
- * fsg_init / fsg_last_error).  Decode only; there is no deflate compressor
- * here.
+ * fsg_init / fsg_last_error).  This file declares and specifies the reading
+ * side.  The writing side -- fsg_deflate_batch and its sizing and report
+ * calls, whose bodies every inflate reads and whose bytes are this project's
+ * own, not zlib's -- is declared and specified in
+ * flare_deflate_compress_gpu.h, which this header includes at its end.
  *
  * Reference interface: flare's GzipDecompress and ZlibDecompress
  * (COMPRESS_TYPE_GZIP = 2 and COMPRESS_TYPE_ZLIB = 3, flare/rpc/options.proto,
@@ -116,4 +119,7 @@ int fsg_adler32_batch(const uint8_t *d_in, const uint64_t *d_in_off,
 #ifdef __cplusplus
 }
 #endif
+
+#include "flare_deflate_compress_gpu.h"
+
 #endif /* FLARE_DEFLATE_GPU_H_ */
