@@ -28,6 +28,50 @@ constexpr u32 kAhead = 7;                    // chunks prefetched per iteration
 // what a lane without input prefetches
 __device__ u32x4 g_dummy_chunk[1];
 
+// ---- the walk's tag rule (the role of char_table, snappy.cc:516-549): per
+// tag byte c the advance (tag byte + extra bytes + a short literal's bytes,
+// <= kMaxAdv) and the output length (<= kMaxLen).  The four long literal tags
+// (0xF0, 0xF4, 0xF8, 0xFC) have advance and length 0, which is also their
+// flag: the unrolled walk stays on such a tag and the long-literal path after
+// it takes the length from the ring.  Every other advance is non-zero.
+constexpr u32 kMaxAdv = 65, kMaxLen = 64;
+struct TagRule {
+  u32 adv, len;
+};
+__host__ __device__ constexpr TagRule tag_rule(u32 c) {
+  const u32 type = c & 3, l0 = (c >> 2) + 1;
+  if (type == 0) return l0 > 60 ? TagRule{0, 0} : TagRule{1 + l0, l0};
+  if (type == 1) return TagRule{2, 4 + ((c >> 2) & 7)};
+  return TagRule{type == 2 ? 3u : 5u, l0};
+}
+// The walk does not look the advance up: it computes it, already shifted to
+// the position field of its accumulator (bit kPosShift), from a "pick" byte
+// -- c itself for a literal, (advance - 2) * 4 for a copy, taken by one bit
+// field extract at 8 * type out of c | kAdvPick -- as (pick << 4) + (2 << 6).
+// Long literals and lanes past their limit do not advance (tag_stay).
+constexpr u32 kPosShift = 6;
+constexpr u32 kAdvPick = 0x0c040000u;  // bytes 1-3: (advance - 2) * 4 of copy types 1-3
+// byte (c & 3) of w
+__host__ __device__ constexpr u32 type_byte(u32 w, u32 c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  // (v_bfe_u32 takes the low 5 bits of its offset; written out, the compiler
+  // makes four instructions of the line below)
+  if (!__builtin_is_constant_evaluated()) return __builtin_amdgcn_ubfe(w, c << 3, 8);
+#endif
+  return (w >> ((c << 3) & 31u)) & 0xffu;
+}
+__host__ __device__ constexpr u32 tag_pick(u32 c) { return type_byte(c | kAdvPick, c); }
+__host__ __device__ constexpr bool tag_stay(u32 c, u32 thr = 1) { return ((c & 0xf3u) ^ 0xf0u) < thr; }
+__host__ __device__ constexpr u32 tag_advance(u32 c) {
+  return tag_stay(c) ? 0u : (tag_pick(c) << (kPosShift - 2)) + (2u << kPosShift);
+}
+constexpr bool tag_advance_is_rule() {
+  for (u32 c = 0; c < 256; ++c)
+    if (tag_advance(c) != tag_rule(c).adv << kPosShift || tag_rule(c).adv > kMaxAdv || tag_rule(c).len > kMaxLen) return false;
+  return true;
+}
+static_assert(tag_advance_is_rule(), "the computed advance differs from the tag rule");
+
 }  // namespace
 
 // ===========================================================================
@@ -248,11 +292,12 @@ __attribute__((amdgpu_waves_per_eu(kLean ? 6 : 1))) void index_kernel(
   // 52 used), too many to fit beside the execution pass's waves.
   extern __shared__ u32 idx_dyn_lds[];
   __shared__ u32 ring_s[kLean ? 1 : kW][kLean ? 1 : (kRD + 5) * kWave];
-  __shared__ u32 tagtab_s[kLean ? 1 : 256];
+  __shared__ u8 lentab_s[kLean ? 1 : 256];
   __shared__ u32 bmr_s[kLean ? 1 : kW][kLean ? 1 : kBW * kWave];
   const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   u32* const ring = kLean ? idx_dyn_lds + wv * (kRD + 5) * kWave : ring_s[wv];
-  u32* const tagtab = kLean ? idx_dyn_lds + kW * (kRD + 5) * kWave : tagtab_s;
+  // (lean: the first 256 bytes of the 256 words idx_lean_lds_bytes() keeps between the rings)
+  u8* const lentab = kLean ? reinterpret_cast<u8*>(idx_dyn_lds + kW * (kRD + 5) * kWave) : lentab_s;
   u32* const bmr = kLean ? idx_dyn_lds + kW * (kRD + 5) * kWave + 256 + wv * kBW * kWave : bmr_s[wv];
 
   const u32 lane = threadIdx.x & 63;
@@ -266,40 +311,24 @@ __attribute__((amdgpu_waves_per_eu(kLean ? 6 : 1))) void index_kernel(
   const u8* const ring_b0 = reinterpret_cast<const u8*>(kLean ? idx_dyn_lds : &ring_s[0][0]);
   u32* const bmr_w0 = kLean ? idx_dyn_lds + kW * (kRD + 5) * kWave + 256 : &bmr_s[0][0];
   const u32 ring_lane = (wv * (kRD + 5) * kWave + lane) * 4, bmr_lane = wv * kBW * kWave + lane;
-  // Tag table (the role of char_table, snappy.cc:516-549): per tag byte c one
-  // word that a single add applies to the walk's packed accumulator: bits
-  // 16-31 the output length (<= kMaxLen), bits 6-15 the advance (tag byte +
-  // extra bytes + a short literal's bytes, <= kMaxAdv), bits 0-5 zero.  The
-  // advance sits at bit 6 so that the accumulator's position field, masked,
-  // IS the ring address of its dword ([dword][lane]: byte P of a lane is at
-  // (P >> 2) * 256 + lane * 4 + (P & 3), and ((P << 6) & 0x3f00) is the first
-  // term).  The four long literal tags (0xF0, 0xF4, 0xF8, 0xFC) hold 0, which
-  // is also their flag: the unrolled walk stays on such a tag and the
-  // long-literal path after it takes its length from the ring.  Every other
-  // entry is non-zero.
-  constexpr u32 kMaxAdv = 65, kMaxLen = 64, kPosShift = 6;
-  // The position field starts an iteration at the low 8 bits of the ring
+  // The walk's accumulator holds the ring position at bit kPosShift = 6
+  // (tag_advance gives the advance there), so that the position field,
+  // masked, IS the ring address of its dword ([dword][lane]: byte P of a lane
+  // is at (P >> 2) * 256 + lane * 4 + (P & 3), and ((P << 6) & 0x3f00) is the
+  // first term).  It starts an iteration at the low 8 bits of the ring
   // position and advances by at most kMaxDist (the clamp of the limit) plus
-  // one tag: it stays inside bits 6-15, so no carry reaches the length, and
-  // the length half holds an iteration's sum.
+  // one tag: it stays inside bits 6-15, the half the limit compare looks at.
+  // The iteration's output length is summed in a register of its own.
   constexpr u32 kMaxDist = 255;
-  static_assert(255 + kMaxDist + kMaxAdv < (1u << (16 - kPosShift)), "position field of the packed accumulator overflows");
-  static_assert(kIdxTags * kMaxLen <= 0xffffu, "length half of the packed accumulator overflows");
+  static_assert(255 + kMaxDist + kMaxAdv < (1u << (16 - kPosShift)), "position field of the accumulator overflows");
+  static_assert(kIdxTags * kMaxLen <= 0xffffu, "an iteration's length sum overflows");
+  // Length table: tag_rule(c).len per tag byte, read when the byte arrives
+  // and added in the shadow of the next byte's read (off the tag-to-tag
+  // chain).
 #pragma unroll
   for (u32 q = 0; q < 4 / kW; ++q) {
-    const u32 c = threadIdx.x * (4 / kW) + q, type = c & 3, l0 = (c >> 2) + 1;
-    u32 adv, len;
-    if (type == 0) {
-      len = l0 > 60 ? 0 : l0;
-      adv = l0 > 60 ? 0 : 1 + l0;
-    } else if (type == 1) {
-      adv = 2;
-      len = 4 + ((c >> 2) & 7);
-    } else {
-      adv = type == 2 ? 3 : 5;
-      len = l0;
-    }
-    tagtab[c] = (len << 16) | (adv << kPosShift);
+    const u32 c = threadIdx.x * (4 / kW) + q;
+    lentab[c] = (u8)tag_rule(c).len;
   }
   __syncthreads();
   // planned with a walk order: lane g walks message walk_perm[g], the
@@ -410,12 +439,13 @@ __attribute__((amdgpu_waves_per_eu(kLean ? 6 : 1))) void index_kernel(
       const u32 ring_end = 16 * wend >= 4 + ibal ? 16 * wend - 4 - ibal : 0u;
       lim = (wend > last_chunk || ring_end > n_in) ? n_in : ring_end;
     }
-    // The unrolled walk keeps one packed accumulator per iteration, in the
-    // tag table's format: output length of the iteration so far in bits
-    // 16-31, ring position in bits 6-15 (the low 8 bits of ip + ibal at the
-    // iteration's start, plus the advance since; the static_asserts at the
-    // table bound both fields).  A tag costs one byte read of the ring, one
-    // table read and one add; the walk never looks at a copy's offset bytes.
+    // The unrolled walk keeps the ring position in bits 6-15 of one
+    // accumulator (the low 8 bits of ip + ibal at the iteration's start, plus
+    // the advance since; the static_asserts above bound it) and the output
+    // length of the iteration so far in another register.  A tag costs one
+    // byte read of the ring on the tag-to-tag chain; the advance is computed
+    // from the byte (tag_advance), the length read from the table beside the
+    // chain; the walk never looks at a copy's offset bytes.
     // The 16-bit compare `pos < lim_pos` is `ip < lim`.  The limit's distance
     // is clamped to kMaxDist: the ring holds no more than 256 bytes from the
     // start, and a tag the clamp cuts off waits for the next iteration.
@@ -427,28 +457,50 @@ __attribute__((amdgpu_waves_per_eu(kLean ? 6 : 1))) void index_kernel(
     auto tag_read = [&](u32 a) -> u32 {
       return ring_b0[(a & ((kRD - 1) << 8)) + (__builtin_amdgcn_ubfe(a, kPosShift, 2) | ring_lane)];
     };
-    // Software-pipelined: tag j+1's ring read is issued (in program order)
-    // before tag j's ds_or, so the LDS latency overlaps it; the compiler does
-    // not move LDS reads above the atomic.  The read after the last tag shows
-    // the long-literal path what the lane stands on.
-    u32 acc = pos_it << kPosShift;
+    // Software-pipelined: tag j+1's ring read is issued before tag j's ds_or
+    // and length add, so the LDS latency overlaps them.  The read after the
+    // last tag shows the long-literal path what the lane stands on.
+    u32 acc = pos_it << kPosShift, len_it = 0;
     u32 c = tag_read(acc);
+    // What a step knows before its byte arrives is prepared while the read
+    // is in flight: the limit compare (a lane past its limit stays, by the
+    // threshold of tag_stay) and the position plus the advance's constant 2.
+    bool look = (u16)acc < lim_pos;
+    u32 thr = look ? 1u : 0x100u, acc2 = acc + (2u << kPosShift);
+    // (the empty statements and the scheduling barrier pin that order, which
+    // the compiler's scheduler does not keep: everything above such a
+    // statement is issued before the wait for c)
+    asm volatile("" : "+v"(c), "+v"(thr), "+v"(acc2));
 #pragma unroll
     for (int j = 0; j < kIdxTags; ++j) {
       // The walk advances over every tag below lim whether or not it will
       // pass the iteration's checks, so they stay off the dependency chain.
-      // A long literal's entry is 0: the lane stays on it, looks at it again
-      // in every remaining slot and ORs the same bit again.
-      const u32 e = tagtab[c];
-      const bool look = (u16)acc < lim_pos;
-      const u32 acc_next = acc + (look ? e : 0u);
-      c = tag_read(acc_next);
+      // A long literal does not advance: the lane stays on it, looks at it
+      // again in every remaining slot and ORs the same bit again.
+      const u32 len_rd = lentab[c];
+      const bool stay = tag_stay(c, thr);
+      u32 acc_next = stay ? acc : (tag_pick(c) << (kPosShift - 2)) + acc2;
+      // (opaque: knowing that a staying lane reads the byte it has, the
+      // compiler turns the select into a branch around the read)
+      asm volatile("" : "+v"(acc_next));
+      const u32 c_next = tag_read(acc_next);
+      __builtin_amdgcn_sched_barrier(0);
+      // ---- in the shadow of that read: the tag's bit, its length, and the
+      // next step's preparation
+      u32 len = len_rd;
+      asm volatile("" : "+v"(len), "+v"(acc_next));
       const u32 at = ip_base + __builtin_amdgcn_ubfe(acc, kPosShift, 16 - kPosShift);
       atomicOr(&bmr_w0[(__builtin_amdgcn_ubfe(at, 5, kBWlog) << 6) + bmr_lane], look ? 1u << (at & 31) : 0u);
+      len_it += stay ? 0u : len;
       acc = acc_next;
+      c = c_next;
+      look = (u16)acc < lim_pos;
+      thr = look ? 1u : 0x100u;
+      acc2 = acc + (2u << kPosShift);
+      asm volatile("" : "+v"(c), "+v"(thr), "+v"(acc2), "+v"(len_it) : : "memory");
     }
     ip = ip_base + __builtin_amdgcn_ubfe(acc, kPosShift, 16 - kPosShift);
-    op = op_it + (acc >> 16);
+    op = op_it + len_it;
 
     // ---------- long literals (tags 0xF0/0xF4/0xF8/0xFC), off the unrolled
     // walk: a wave-uniform branch for the lanes that stand on one below lim.
