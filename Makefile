@@ -6,8 +6,8 @@ PKG      := flare-cpp_amd
 LIB      := $(PKG)/lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall
 CSRC     := $(PKG)/csrc/capi.hip $(PKG)/csrc/snappy_decode.hip $(PKG)/csrc/snappy_decode_v3.hip $(PKG)/csrc/snappy_decode_v4.hip $(PKG)/csrc/snappy_decode_partial.hip \
-            $(PKG)/csrc/snappy_encode.hip $(PKG)/csrc/snappy_encode_v3.hip $(PKG)/csrc/snappy_encode_wave.hip $(PKG)/csrc/gather.hip $(PKG)/csrc/pack.hip $(PKG)/csrc/lz4.hip $(PKG)/csrc/lz4_decode2.hip $(PKG)/csrc/lz4_encode_wave.hip $(PKG)/csrc/lz4_frame.hip $(PKG)/csrc/inflate.hip $(PKG)/csrc/deflate.hip
-CHDRS    := $(wildcard $(PKG)/csrc/*.h) include/flare_snappy_gpu.h include/flare_lz4_gpu.h include/flare_deflate_gpu.h include/flare_deflate_compress_gpu.h
+            $(PKG)/csrc/snappy_encode.hip $(PKG)/csrc/snappy_encode_v3.hip $(PKG)/csrc/snappy_encode_wave.hip $(PKG)/csrc/gather.hip $(PKG)/csrc/pack.hip $(PKG)/csrc/lz4.hip $(PKG)/csrc/lz4_decode2.hip $(PKG)/csrc/lz4_encode_wave.hip $(PKG)/csrc/lz4_frame.hip $(PKG)/csrc/inflate.hip $(PKG)/csrc/deflate.hip $(PKG)/csrc/deflate_level.hip
+CHDRS    := $(wildcard $(PKG)/csrc/*.h) include/flare_snappy_gpu.h include/flare_lz4_gpu.h include/flare_deflate_gpu.h include/flare_deflate_compress_gpu.h include/flare_deflate_level_gpu.h
 OBJDIR   := build/obj
 
 all: gpu host datagen oracle cpptests hostbench echobench
@@ -36,7 +36,7 @@ $(LIB)/libflare_rpc_snappy.so: $(HOST_SRC) $(HOST_HDRS) $(LIB)/libflare_snappy_g
 
 # C++ tests mirroring test/rpc/rpc_snappy_compress_test.cc and the baidu_std /
 # rpc_dump framing (run by pytest)
-cpptests: build/test_rpc_snappy_compress build/test_baidu_std build/test_pack_output build/test_path_report build/test_lz4_frame_handler build/test_gzip_handler
+cpptests: build/test_rpc_snappy_compress build/test_baidu_std build/test_pack_output build/test_path_report build/test_lz4_frame_handler build/test_gzip_handler build/test_gzip_options
 
 # the LZ4 frame CompressHandler (policy::Lz4FrameCompress / Lz4FrameDecompress), host only
 build/test_lz4_frame_handler: tests/cpp/test_lz4_frame_handler.cc $(HOST_HDRS) $(LIB)/libflare_rpc_snappy.so
@@ -47,6 +47,13 @@ build/test_lz4_frame_handler: tests/cpp/test_lz4_frame_handler.cc $(HOST_HDRS) $
 
 # the gzip / zlib CompressHandlers (policy::GzipCompress and its kin), host only
 build/test_gzip_handler: tests/cpp/test_gzip_handler.cc $(HOST_HDRS) $(LIB)/libflare_rpc_snappy.so
+	@mkdir -p build
+	$(HOSTCXX) -o $@ $< -I$(PKG)/host -L$(LIB) -lflare_rpc_snappy -lflare_snappy_gpu \
+	  -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$(abspath $(LIB)) -Wl,-rpath,'$$ORIGIN/../$(LIB)' \
+	  -Wl,-rpath,/opt/rocm/lib -pthread
+
+# GzipCompress with GzipCompressOptions (format and compression level), host only
+build/test_gzip_options: tests/cpp/test_gzip_options.cc $(HOST_HDRS) $(LIB)/libflare_rpc_snappy.so
 	@mkdir -p build
 	$(HOSTCXX) -o $@ $< -I$(PKG)/host -L$(LIB) -lflare_rpc_snappy -lflare_snappy_gpu \
 	  -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$(abspath $(LIB)) -Wl,-rpath,'$$ORIGIN/../$(LIB)' \
@@ -128,8 +135,9 @@ $(LIB)/libflare_snappy_gpu_stamps.so: $(CSRC) $(CHDRS)
 # after phase 1 (parse) and after phase 2 (code build); never loaded by the
 # product path.
 deflate_phases: $(LIB)/libflare_snappy_gpu_deflate_p1.so $(LIB)/libflare_snappy_gpu_deflate_p2.so
-$(LIB)/libflare_snappy_gpu_deflate_p%.so: $(PKG)/csrc/deflate.hip $(CHDRS) $(LIB)/libflare_snappy_gpu.so
+$(LIB)/libflare_snappy_gpu_deflate_p%.so: $(PKG)/csrc/deflate.hip $(PKG)/csrc/deflate_level.hip $(CHDRS) $(LIB)/libflare_snappy_gpu.so
 	@mkdir -p $(LIB) build/deflate_p$*
-	$(HIPCC) $(HIPFLAGS) -DFSG_DEFLATE_PHASES=$* -c $< -o build/deflate_p$*/deflate.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ build/deflate_p$*/deflate.o $(filter-out $(OBJDIR)/deflate.o,$(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/%.o,$(CSRC)))
+	$(HIPCC) $(HIPFLAGS) -DFSG_DEFLATE_PHASES=$* -c $(PKG)/csrc/deflate.hip -o build/deflate_p$*/deflate.o
+	$(HIPCC) $(HIPFLAGS) -DFSG_DEFLATE_PHASES=$* -c $(PKG)/csrc/deflate_level.hip -o build/deflate_p$*/deflate_level.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ build/deflate_p$*/deflate.o build/deflate_p$*/deflate_level.o $(filter-out $(OBJDIR)/deflate.o $(OBJDIR)/deflate_level.o,$(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/%.o,$(CSRC)))
 .PHONY: deflate_phases

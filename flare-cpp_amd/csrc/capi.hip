@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "../../include/flare_deflate_gpu.h"
+#include "../../include/flare_deflate_level_gpu.h"
 #include "../../include/flare_lz4_gpu.h"
 #include "../../include/flare_snappy_gpu.h"
 #include "deflate_format.h"
@@ -736,6 +737,16 @@ size_t fsg_deflate_workspace_bytes(uint32_t n_msgs, uint64_t total_in_bytes) {
 int fsg_deflate_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_msgs,
                       uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status,
                       uint32_t format, void* d_workspace, size_t workspace_bytes, void* stream) {
+  return fsg_deflate_batch_level(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_len, d_status, format,
+                                 FSG_DEFLATE_LEVEL_FAST, d_workspace, workspace_bytes, stream);
+}
+
+// (include/flare_deflate_level_gpu.h)
+int fsg_deflate_batch_level(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_msgs,
+                            uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status,
+                            uint32_t format, uint32_t level, void* d_workspace, size_t workspace_bytes,
+                            void* stream) {
+  if (level > FSG_DEFLATE_LEVEL_BEST) return FSG_ERR_INVALID_ARG;
   if (format > FSG_DEFLATE_GZIP) return FSG_ERR_INVALID_ARG;
   if (n_msgs == 0) return FSG_SUCCESS;
   if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len || !d_status || !d_workspace)
@@ -743,7 +754,7 @@ int fsg_deflate_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint3
   if (reinterpret_cast<uintptr_t>(d_workspace) & 15u) return FSG_ERR_INVALID_ARG;
   if (fsg::deflate_unit_capacity(n_msgs, workspace_bytes) == 0) return FSG_ERR_INVALID_ARG;
   return record(fsg::launch_deflate(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_len, d_status, format,
-                                    d_workspace, workspace_bytes, (hipStream_t)stream),
+                                    level, d_workspace, workspace_bytes, (hipStream_t)stream),
                 "fsg_deflate_batch");
 }
 

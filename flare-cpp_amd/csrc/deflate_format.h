@@ -29,6 +29,9 @@
 //   position, a match moves by its length, a literal by 1; a match that
 //   crosses the window's end sets the next window's first position.  All
 //   positions of a window are inserted after it, in ascending order.
+//   Levels.  That is level 1, what fsg_deflate_batch writes.  Level 0 (stored
+//   units only) and level 2 (another parse, everything else unchanged) are
+//   stated at "levels" below.
 //
 // Lanes.  Functions with (lane, nlanes) are called by the host with (0, 1) and
 // by all 64 lanes of a wave together, arrays in LDS, under the rules
@@ -150,6 +153,80 @@ INFL_HD uint32_t token_at(const R& rd, uint32_t n, uint32_t p, const uint16_t* t
   if (k > limit) k = limit;
   return k >= kMinMatch ? (k | (p - c) << 9) : lit;
 }
+
+// ---- levels.  Level 1 is the stream above.  Level 0 writes every unit as a
+// stored block, with no parse and no code build: a body's length is exactly
+// max_length(n, format).  Level 2 keeps units, blocks, choice, codes, header,
+// emit, wrappers and bound; only the parse differs:
+//   Table.  kTableEntries 32-bit words: the low half is the newer candidate
+//   position of the slot, the high half the older one, kNoPos in a half that
+//   is empty.  The hash is hash4.
+//   Token.  Both candidates are tried under level 1's validity rule; each
+//   one's length is the common prefix, at most 258 and the bytes left.  The
+//   longer wins, the newer (nearer) on equal lengths; a match from 4 bytes on.
+//   One lazy step.  With r[] the window's tokens as just defined, position i
+//   becomes the literal of its byte when r[i] is a match, i + 1 lies in the
+//   same window, r[i + 1] is a match and longer than r[i].  The decision
+//   reads the undeferred r[i + 1]; the window's last position never defers.
+//   The greedy chain then walks the deferred tokens as at level 1.
+//   Insert.  After the window, every slot that a position of the window (4
+//   bytes left) hashes to becomes insert_word(old, highest such position):
+//   one new entry per slot and window, the previous older candidate drops out.
+constexpr uint32_t kLevelStored = 0, kLevelFast = 1, kLevelBest = 2, kMaxLevel = 2;
+constexpr uint32_t kEmptyPair = kNoPos | kNoPos << 16;
+
+// The common prefix of the unit's bytes at p and at c < p, at most limit.
+template <class R>
+INFL_HD uint32_t common_prefix(const R& rd, uint32_t p, uint32_t c, uint32_t limit) {
+  uint32_t k = 0;
+  while (k < limit) {
+    const uint32_t x = rd.load32(p + k) ^ rd.load32(c + k);
+    if (x) {
+      k += (uint32_t)__builtin_ctz(x) >> 3;
+      break;
+    }
+    k += 4;
+  }
+  return k > limit ? limit : k;
+}
+
+// Level 2's token at unit position p < n, before the lazy step.  table: the
+// kTableEntries words of the state before p's window.  *four: the bytes
+// p .. p+3.  *word: the slot's word when p has 4 bytes left (what insert_word
+// takes after the window), else untouched.  The second compare is skipped
+// when the first reached the limit: an equal length would lose to it.
+template <class R>
+INFL_HD uint32_t token_at2(const R& rd, uint32_t n, uint32_t p, const uint32_t* table, uint32_t* four,
+                           uint32_t* word) {
+  const uint32_t mine = rd.load32(p);
+  *four = mine;
+  const uint32_t lit = kTokLit | (mine & 0xffu);
+  if (n - p < kMinMatch) return lit;
+  const uint32_t w = table[hash4(mine)];
+  *word = w;
+  const uint32_t newer = w & 0xffffu, older = w >> 16;
+  const uint32_t limit = n - p < kMaxMatch ? n - p : kMaxMatch;
+  uint32_t k = 0, c = newer;
+  if (newer != kNoPos && p - newer <= kMaxDist) k = common_prefix(rd, p, newer, limit);
+  if (k < limit && older != kNoPos && p - older <= kMaxDist) {
+    const uint32_t k1 = common_prefix(rd, p, older, limit);
+    if (k1 > k) {
+      k = k1;
+      c = older;
+    }
+  }
+  return k >= kMinMatch ? (k | (p - c) << 9) : lit;
+}
+
+// The lazy step: position i's token from r = r[i] and next = r[i + 1]
+// (has_next: i + 1 is a position of the same window); byte: the byte at i.
+INFL_HD uint32_t defer_token(uint32_t r, uint32_t next, bool has_next, uint32_t byte) {
+  const bool defer = has_next && !(r & kTokLit) && !(next & kTokLit) && tok_length(next) > tok_length(r);
+  return defer ? (kTokLit | (byte & 0xffu)) : r;
+}
+
+// The slot's word after a window whose highest position in the slot is p.
+INFL_HD uint32_t insert_word(uint32_t old, uint32_t p) { return (old & 0xffffu) << 16 | p; }
 
 // ---- the arrays of one unit's code build (LDS on the device, 8 KiB)
 constexpr uint32_t kLitSyms = 286, kDistSyms = 30, kClSyms = 19;

@@ -139,7 +139,8 @@ hipError_t launch_inflate_sum(const u8* in, const u64* in_off, const u32* in_len
 size_t deflate_workspace_bytes(u32 n_msgs, u64 total_in_bytes);
 u64 deflate_unit_capacity(u32 n_msgs, size_t ws_bytes);
 hipError_t launch_deflate(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out, const u64* out_off,
-                          u32* out_len, i32* status, u32 format, void* ws, size_t ws_bytes, hipStream_t stream);
+                          u32* out_len, i32* status, u32 format, u32 level, void* ws, size_t ws_bytes,
+                          hipStream_t stream);  // level: defl::kLevelStored / Fast / Best (deflate_format.h)
 struct DeflateHeaderCounts {
   u32 units, stored, fixed, dynamic, overflow;
 };

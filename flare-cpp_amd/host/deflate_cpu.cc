@@ -31,6 +31,7 @@ struct UnitReader {
 
 struct Scratch {
   uint16_t table[kTableEntries];
+  uint32_t pairs[kTableEntries];  // level 2's table
   Build b;
   std::vector<uint32_t> tokens, win;
 };
@@ -60,10 +61,54 @@ void parse_unit(const UnitReader& rd, Scratch& s) {
   count_token(&s.b, kTokEnd);
 }
 
+// Phase 1 at level 2: two candidates per slot and one lazy step inside the
+// window (deflate_format.h, "levels").
+void parse_unit2(const UnitReader& rd, Scratch& s) {
+  for (uint32_t i = 0; i < kTableEntries; ++i) s.pairs[i] = kEmptyPair;
+  memset(&s.b, 0, sizeof s.b);
+  s.tokens.clear();
+  const uint32_t n = rd.n;
+  uint32_t entry = 0;
+  for (uint32_t base = 0; base < n; base += kWindow) {
+    const uint32_t cnt = n - base < kWindow ? n - base : kWindow;
+    uint32_t r[kWindow + 1], rec[kWindow], four[kWindow], word[kWindow];
+    for (uint32_t i = 0; i < cnt; ++i) r[i] = token_at2(rd, n, base + i, s.pairs, &four[i], &word[i]);
+    r[cnt] = kTokLit;
+    for (uint32_t i = 0; i < cnt; ++i) rec[i] = defer_token(r[i], r[i + 1], i + 1 < cnt, four[i]);
+    uint32_t cur = entry;
+    while (cur < cnt) {
+      s.tokens.push_back(rec[cur]);
+      count_token(&s.b, rec[cur]);
+      cur += tok_advance(rec[cur]);
+    }
+    entry = cur - cnt;
+    // every word comes from the state before the window; the highest position of a slot lands last
+    for (uint32_t i = 0; i < cnt; ++i)
+      if (n - (base + i) >= kMinMatch) s.pairs[hash4(four[i])] = insert_word(word[i], base + i);
+  }
+  s.tokens.push_back(kTokEnd);
+  count_token(&s.b, kTokEnd);
+}
+
+void write_stored_unit(const uint8_t* in, uint32_t n, bool last, std::vector<uint8_t>* out) {
+  uint8_t h[5];
+  write_stored_head(n, last, h);
+  out->insert(out->end(), h, h + 5);
+  out->insert(out->end(), in, in + n);
+}
+
 // Phases 2 and 3 for one unit; its bytes are appended to out.
-uint32_t compress_unit(const uint8_t* in, uint32_t n, bool last, Scratch& s, std::vector<uint8_t>* out) {
+uint32_t compress_unit(uint32_t level, const uint8_t* in, uint32_t n, bool last, Scratch& s,
+                       std::vector<uint8_t>* out) {
+  if (level == kLevelStored) {
+    if (out) write_stored_unit(in, n, last, out);
+    return kStored;
+  }
   const UnitReader rd{in, n};
-  parse_unit(rd, s);
+  if (level == kLevelBest)
+    parse_unit2(rd, s);
+  else
+    parse_unit(rd, s);
   Build* b = &s.b;
   build_lengths(b->hist, kLitSyms, 15, b->len, b, 0, 1);
   build_lengths(b->hist + kDistBase, kDistSyms, 15, b->len + kDistBase, b, 0, 1);
@@ -73,10 +118,7 @@ uint32_t compress_unit(const uint8_t* in, uint32_t n, bool last, Scratch& s, std
   const Choice c = choose_block(n, last, dyn + header, fix);
   if (!out) return c.type;
   if (c.type == kStored) {
-    uint8_t h[5];
-    write_stored_head(n, last, h);
-    out->insert(out->end(), h, h + 5);
-    out->insert(out->end(), in, in + n);
+    write_stored_unit(in, n, last, out);
     return c.type;
   }
   if (c.type == kFixed) {
@@ -108,9 +150,14 @@ extern "C" {
 
 size_t fsh_cpu_deflate_bound(size_t n, uint32_t format) { return (size_t)defl::max_length(n, format); }
 
-int fsh_cpu_deflate(uint32_t format, const void* in_, size_t n, void* out_, size_t cap, uint64_t* len) {
+int fsh_cpu_deflate(uint32_t format, const void* in, size_t n, void* out, size_t cap, uint64_t* len) {
+  return fsh_cpu_deflate_level(format, kLevelFast, in, n, out, cap, len);
+}
+
+int fsh_cpu_deflate_level(uint32_t format, uint32_t level, const void* in_, size_t n, void* out_, size_t cap,
+                          uint64_t* len) {
   *len = 0;
-  if (format > kGzip) return infl::kStCorrupt;
+  if (format > kGzip || level > kMaxLevel) return infl::kStCorrupt;
   const uint8_t* in = static_cast<const uint8_t*>(in_);
   std::vector<uint8_t> body(wrapper_head(format));
   write_wrapper_head(format, body.data());
@@ -119,7 +166,7 @@ int fsh_cpu_deflate(uint32_t format, const void* in_, size_t n, void* out_, size
   for (uint64_t u = 0; u < units; ++u) {
     const uint64_t first = u * kUnit;
     const uint32_t un = (uint32_t)(n - first < kUnit ? n - first : kUnit);
-    compress_unit(in + first, un, u + 1 == units, scratch[0], &body);
+    compress_unit(level, in + first, un, u + 1 == units, scratch[0], &body);
   }
   uint8_t tail[8];
   const uint32_t sum = format == kZlib ? fsh_cpu_adler32(in, n) : format == kGzip ? fsh_cpu_crc32(in, n) : 0u;
@@ -131,21 +178,34 @@ int fsh_cpu_deflate(uint32_t format, const void* in_, size_t n, void* out_, size
   return infl::kStOk;
 }
 
-void fsh_cpu_deflate_unit_types(const void* in_, size_t n, uint64_t counts[3]) {
+void fsh_cpu_deflate_unit_types(const void* in, size_t n, uint64_t counts[3]) {
+  fsh_cpu_deflate_unit_types_level(kLevelFast, in, n, counts);
+}
+
+void fsh_cpu_deflate_unit_types_level(uint32_t level, const void* in_, size_t n, uint64_t counts[3]) {
+  if (level > kMaxLevel) return;
   const uint8_t* in = static_cast<const uint8_t*>(in_);
   std::vector<Scratch> scratch(1);
   const uint64_t units = unit_count(n);
   for (uint64_t u = 0; u < units; ++u) {
     const uint64_t first = u * kUnit;
     const uint32_t un = (uint32_t)(n - first < kUnit ? n - first : kUnit);
-    ++counts[compress_unit(in + first, un, u + 1 == units, scratch[0], nullptr)];
+    ++counts[compress_unit(level, in + first, un, u + 1 == units, scratch[0], nullptr)];
   }
 }
 
-size_t fsh_cpu_deflate_tokens(const void* in_, size_t n, uint32_t* tokens, size_t cap) {
-  if (n > kUnit) return 0;
+size_t fsh_cpu_deflate_tokens(const void* in, size_t n, uint32_t* tokens, size_t cap) {
+  return fsh_cpu_deflate_tokens_level(kLevelFast, in, n, tokens, cap);
+}
+
+size_t fsh_cpu_deflate_tokens_level(uint32_t level, const void* in_, size_t n, uint32_t* tokens, size_t cap) {
+  if (n > kUnit || level < kLevelFast || level > kMaxLevel) return 0;
   std::vector<Scratch> scratch(1);
-  parse_unit(UnitReader{static_cast<const uint8_t*>(in_), (uint32_t)n}, scratch[0]);
+  const UnitReader rd{static_cast<const uint8_t*>(in_), (uint32_t)n};
+  if (level == kLevelBest)
+    parse_unit2(rd, scratch[0]);
+  else
+    parse_unit(rd, scratch[0]);
   const size_t cnt = scratch[0].tokens.size() - 1;
   if (cnt > cap) return 0;
   if (cnt) memcpy(tokens, scratch[0].tokens.data(), cnt * 4);
@@ -160,7 +220,7 @@ uint64_t fsh_cpu_deflate_limited(const void* in_, size_t n) {
   for (uint64_t u = 0; u < units; ++u) {
     const uint64_t first = u * kUnit;
     const uint32_t un = (uint32_t)(n - first < kUnit ? n - first : kUnit);
-    compress_unit(in + first, un, u + 1 == units, scratch[0], nullptr);
+    compress_unit(kLevelFast, in + first, un, u + 1 == units, scratch[0], nullptr);
     limited += scratch[0].b.limited;
   }
   return limited;

@@ -14,13 +14,13 @@ namespace {
 
 constexpr uint32_t kZlibFormat = 1, kGzipFormat = 2;  // FSG_INFLATE_ZLIB, FSG_INFLATE_GZIP
 
-bool Deflate(uint32_t format, const cord_buf& in, cord_buf* out) {
+bool Deflate(uint32_t format, const cord_buf& in, cord_buf* out, uint32_t level = 1) {
   const size_t n = in.size();
   std::vector<uint8_t> src(n);
   in.copy_to(src.data(), n);
   std::vector<uint8_t> body(fsh_cpu_deflate_bound(n, format));
   uint64_t len = 0;
-  if (fsh_cpu_deflate(format, src.data(), n, body.data(), body.size(), &len) != 0) return false;
+  if (fsh_cpu_deflate_level(format, level, src.data(), n, body.data(), body.size(), &len) != 0) return false;
   return out->append(body.data(), len) == 0;
 }
 
@@ -57,6 +57,20 @@ bool DecompressMessage(bool (*f)(const cord_buf&, cord_buf*), const char* what, 
 }  // namespace
 
 bool GzipCompress(const cord_buf& in, cord_buf* out) { return Deflate(kGzipFormat, in, out); }
+bool GzipCompress(const cord_buf& in, cord_buf* out, const GzipCompressOptions* options) {
+  if (!options) return GzipCompress(in, out);
+  const int z = options->compression_level;
+  if (z < -1 || z > 9) return false;
+  const uint32_t level = z == 0 ? 0u : z >= 1 && z <= 3 ? 1u : 2u;
+  uint32_t format;
+  if (options->format == GzipCompressOptions::GZIP)
+    format = kGzipFormat;
+  else if (options->format == GzipCompressOptions::ZLIB)
+    format = kZlibFormat;
+  else
+    return false;
+  return Deflate(format, in, out, level);
+}
 bool GzipDecompress(const cord_buf& in, cord_buf* out) { return Inflate(kGzipFormat, in, out); }
 bool ZlibCompress(const cord_buf& in, cord_buf* out) { return Deflate(kZlibFormat, in, out); }
 bool ZlibDecompress(const cord_buf& in, cord_buf* out) { return Inflate(kZlibFormat, in, out); }

@@ -2,9 +2,13 @@
 // COMPRESS_TYPE_ZLIB (3), shaped like the reference's (flare
 // rpc/policy/gzip_compress.h: GzipCompress / GzipDecompress / ZlibCompress /
 // ZlibDecompress, same meaning of arguments and return values), written
-// against those signatures only.  The reference's optional third argument, a
-// GzipCompressOptions* with a level and a format, is not taken: there is one
-// level, and the format is the function's.
+// against those signatures only.  The reference's third overload,
+// GzipCompress(in, out, const GzipCompressOptions*), is taken too: the format
+// comes from the options and zlib's compression_level maps onto the levels
+// of csrc/deflate_format.h: 0 -> 0 (stored units only), 1 .. 3 (zlib's greedy
+// levels) -> 1, 4 .. 9 and -1 (its lazy levels and its default) -> 2, anything
+// else returns false.  nullptr equals the two-argument function; the two-
+// argument functions write level 1.
 //
 // Compress writes the bodies csrc/deflate_format.h defines (host/deflate_cpu.h:
 // legal gzip / zlib streams that any inflate reads, not zlib's bytes);
@@ -19,6 +23,13 @@
 #include "cord_buf.h"
 
 namespace flare::rpc::policy {
+
+struct GzipCompressOptions {
+  enum Format { GZIP = 1, ZLIB = 2 };
+  Format format = GZIP;
+  int compression_level = -1;
+};
+bool GzipCompress(const cord_buf& in, cord_buf* out, const GzipCompressOptions* options);
 
 bool GzipCompress(const Message& msg, cord_buf* buf);
 bool GzipDecompress(const cord_buf& data, Message* msg);

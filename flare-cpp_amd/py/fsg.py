@@ -18,7 +18,7 @@ LIB_DIR = PKG_DIR / "lib"
 REPO_DIR = PKG_DIR.parent
 HEADER = REPO_DIR / "include" / "flare_snappy_gpu.h"
 HEADERS = (HEADER, REPO_DIR / "include" / "flare_lz4_gpu.h", REPO_DIR / "include" / "flare_deflate_gpu.h",
-           REPO_DIR / "include" / "flare_deflate_compress_gpu.h")
+           REPO_DIR / "include" / "flare_deflate_compress_gpu.h", REPO_DIR / "include" / "flare_deflate_level_gpu.h")
 
 FSG_OK, FSG_CORRUPT, FSG_BAD_HEADER, FSG_SLOT_TOO_SMALL, FSG_IOV_TOO_SMALL = 0, 1, 2, 3, 4
 FSG_FLAG_VALIDATE_ONLY, FSG_FLAG_STRICT_HEADER = 1, 2
@@ -57,6 +57,8 @@ DeflateReport = _report_struct("DeflateReport", (
     "units", "stored_units", "fixed_units", "dynamic_units", "overflow_messages", "unit_entries"))
 # fsg_inflate_batch's and fsg_deflate_batch's formats (FSG_INFLATE_* = FSG_DEFLATE_*, include/flare_deflate_gpu.h)
 INFLATE_RAW, INFLATE_ZLIB, INFLATE_GZIP = 0, 1, 2
+# fsg_deflate_batch_level's levels (FSG_DEFLATE_LEVEL_*, include/flare_deflate_level_gpu.h)
+DEFLATE_LEVEL_STORED, DEFLATE_LEVEL_FAST, DEFLATE_LEVEL_BEST = 0, 1, 2
 PATH_MAIN, PATH_SINGLE_DESIGN, PATH_NO_WORKSPACE, PATH_FORCED = 0, 1, 2, 3
 
 _SIGS = {
@@ -117,6 +119,7 @@ _SIGS = {
     "fsg_deflate_workspace_bytes": (_sz, [_u32, _u64]),
     "fsg_deflate_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp]),
     "fsg_deflate_report": (_c.c_int, [_vp, _u32, _sz, _c.POINTER(DeflateReport)]),
+    "fsg_deflate_batch_level": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _sz, _vp]),
 }
 
 
@@ -138,7 +141,8 @@ _OPTIONAL = {"fsg_decompress_batch_2s", "fsg_decompress_batch_partial", "fsg_dec
              "fsg_lz4f_compress_report", "fsg_lz4f_decompress_report", "fsg_lz4f_decoded_lengths_batch",
              "fsg_lz4f_max_frame_length_flags", "fsg_lz4f_xxh32_batch", "fsg_lz4f_compress_batch_flags",
              "fsg_inflate_batch", "fsg_inflate_lengths_batch", "fsg_crc32_batch", "fsg_adler32_batch",
-             "fsg_deflate_max_length", "fsg_deflate_workspace_bytes", "fsg_deflate_batch", "fsg_deflate_report"}
+             "fsg_deflate_max_length", "fsg_deflate_workspace_bytes", "fsg_deflate_batch", "fsg_deflate_report",
+             "fsg_deflate_batch_level"}
 
 
 def load_gpu_lib(path: Path | None = None) -> ctypes.CDLL:
@@ -429,10 +433,16 @@ class SnappyGPU:
         return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device or f"cuda:{self.device}")
 
     def deflate(self, d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_len, d_status, workspace,
-                fmt=INFLATE_ZLIB, stream=None):
+                fmt=INFLATE_ZLIB, stream=None, level=None):
         """fsg_deflate_batch: raw deflate, zlib or gzip bodies (INFLATE_*) into
-        slots of deflate_max_length(len, fmt) bytes."""
+        slots of deflate_max_length(len, fmt) bytes.  level (DEFLATE_LEVEL_*):
+        fsg_deflate_batch_level; None calls the level-less entry."""
         ws = 0 if workspace is None else workspace.numel() * workspace.element_size()
+        if level is not None:
+            self._check(self.lib.fsg_deflate_batch_level(
+                _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len),
+                _ptr(d_status), fmt, level, _ptr(workspace), ws, self._stream(stream)), "fsg_deflate_batch_level")
+            return
         self._check(self.lib.fsg_deflate_batch(
             _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len),
             _ptr(d_status), fmt, _ptr(workspace), ws, self._stream(stream)), "fsg_deflate_batch")

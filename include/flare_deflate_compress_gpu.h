@@ -18,7 +18,8 @@
  * Python terms:
  *     d = zlib.decompressobj(wbits); o = d.decompress(body)
  *     o == data and d.eof and not d.unused_data
- * Byte equality with zlib's deflate is not offered at any level.
+ * Byte equality with zlib's deflate is not offered at any level.  This call
+ * writes one level; flare_deflate_level_gpu.h has the call that takes one.
  *
  * The stream in short (deflate_format.h has all of it): the input is cut into
  * units of 65,472 bytes, compressed independently, one deflate block each --

@@ -17,7 +17,10 @@ copies of the library whose unit kernel stops after phase 1 and after phase 2
 times the call under one of them, nothing checked; the differences between
 the three times are the phases.
 
-    python tools/deflate_bench.py [--rows 1x64k,c3] [--launches 10] [--time-only]
+--level 0 or 2 times fsg_deflate_batch_level (include/flare_deflate_level_gpu.h)
+at that level; the rows then carry a "level" key.
+
+    python tools/deflate_bench.py [--rows 1x64k,c3] [--launches 10] [--time-only] [--level 2]
 """
 import argparse
 import json
@@ -47,6 +50,8 @@ def main():
     ap.add_argument("--host-sample", type=int, default=2048)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--time-only", action="store_true", help="the call's median ms per row, nothing checked")
+    ap.add_argument("--level", type=int, default=1, choices=(0, 1, 2),
+                    help="fsg_deflate_batch_level's level; 1 (the default) times the level-less call")
     a = ap.parse_args()
     import torch
     dev = torch.device("cuda", 0)
@@ -55,6 +60,8 @@ def main():
     H = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
     pool = ThreadPoolExecutor(a.threads)
     fmt = fsg.INFLATE_ZLIB
+    lvl = None if a.level == 1 else a.level
+    tag = {} if lvl is None else {"level": lvl}
 
     def timed(fn):
         ms = []
@@ -83,9 +90,11 @@ def main():
         d_ol = torch.zeros(n, dtype=torch.int32, device=dev)
         d_st = torch.zeros(n, dtype=torch.int32, device=dev)
         ws = codec.deflate_workspace(n, raw_bytes)
-        t_call = timed(lambda: codec.deflate(d_in, d_io, d_il, n, d_out, d_oo, d_ol, d_st, ws, fmt=fmt, stream=s))
+        t_call = timed(lambda: codec.deflate(d_in, d_io, d_il, n, d_out, d_oo, d_ol, d_st, ws, fmt=fmt, stream=s,
+                                            level=lvl))
         if a.time_only:
-            print(json.dumps({"row": name, "lib": os.environ.get("FSG_LIB", ""), "call_ms": round(t_call, 4)}), flush=True)
+            print(json.dumps({"row": name, **tag, "lib": os.environ.get("FSG_LIB", ""), "call_ms": round(t_call, 4)}),
+                  flush=True)
             continue
         report = codec.deflate_report(ws, n)
         ok = int((d_st != 0).sum().item()) == 0
@@ -118,7 +127,7 @@ def main():
             host[f"host_zlib{level}_{a.threads}threads_gib_s"] = round(k * size / tn / GIB, 4)
             host[f"host_zlib{level}_1thread_ms_whole_batch"] = round(t1 / k * n * 1e3, 2)
             host[f"host_zlib{level}_{a.threads}threads_ms_whole_batch"] = round(tn / k * n * 1e3, 2)
-        row = {"row": name, "n": n, "size": size, "distinct": distinct, "launches": a.launches,
+        row = {"row": name, **tag, "n": n, "size": size, "distinct": distinct, "launches": a.launches,
                "call_ms": round(t_call, 4), "call_gib_s": round(raw_bytes / (t_call / 1e3) / GIB, 4),
                "ratio": round(raw_bytes / out_bytes, 3), "units": report["units"],
                "stored_units": report["stored_units"], "fixed_units": report["fixed_units"],
