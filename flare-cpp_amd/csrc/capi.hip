@@ -72,6 +72,20 @@ constexpr bool decode_opts_defaults_ok() {
   return true;
 }
 static_assert(fsg::kOptExecPack == 13 && decode_opts_defaults_ok(), "DecodeOpts defaults differ from the option table");
+// and EncodeOpts' (encode_v3_plan.h)
+constexpr bool encode_opts_defaults_ok() {
+  constexpr fsg::EncodeOpts o;
+  const int64_t v[] = {o.encode_wave_min, o.encode_wave_share, o.encode_wave_all_mb,
+                       o.encode_lanes, o.encode_wave_per_cu, o.encode_wave_wg};
+  for (int i = fsg::kOptEncodeWaveMin; i <= fsg::kOptEncodeWaveWg; ++i)
+    if (v[i - fsg::kOptEncodeWaveMin] != kOptDesc[i].dflt) return false;
+  return true;
+}
+static_assert(fsg::kOptEncodeWaveMin == 14 && fsg::kOptEncodeWaveWg == 19 && encode_opts_defaults_ok(),
+              "EncodeOpts defaults differ from the option table");
+static_assert(fsg::kEncRouteMain == FSG_PATH_MAIN && fsg::kEncRouteNoWorkspace == FSG_PATH_NO_WORKSPACE &&
+                  fsg::kEncRouteForced == FSG_PATH_FORCED,
+              "EncodeRoute differs from FSG_PATH_*");
 std::atomic<int64_t> g_opt[fsg::kOptCount];
 // the environment, once, when the library is loaded
 [[maybe_unused]] const bool g_opt_init = [] {
@@ -91,16 +105,6 @@ int find_opt(const char* name) {
 // FSG_ENCODE_KERNEL, changeable with fsg_select_kernels for A/B runs.
 std::atomic<int> g_decode_variant{env_int("FSG_DECODE_KERNEL")};
 std::atomic<int> g_encode_variant{env_int("FSG_ENCODE_KERNEL")};
-// Messages of at least this many bytes (and every fragment of a message over
-// 64 KiB) form the long list, whose units the wave encoder (hash table in
-// LDS, one wave per fragment) and the lane encoder share (wave_quota); the
-// shorter messages go to the lane encoder.  Option encode_wave_min
-// (FSG_ENCODE_WAVE_MIN; 0 = lane encoder only).  Measured on MI355X (A/B, one box): C3
-// compress 108.0 -> 98.4 ms, C5 54.9 -> 39.1 ms.
-fsg::u32 encode_wave_min() {
-  const int64_t v = fsg::opt(fsg::kOptEncodeWaveMin);
-  return v >= 0 ? (fsg::u32)v : 16384u;
-}
 // Test knob: cap the staging region of a split message's fragments (bytes;
 // 0 = slot / fragments).  Small caps force the whole-message fallback pass.
 std::atomic<unsigned> g_region_cap{(unsigned)env_int("FSG_TEST_REGION_CAP")};
@@ -233,12 +237,12 @@ size_t fsg_decompress_workspace_bytes(uint32_t n_msgs, uint64_t total_in_bytes) 
 
 // ---- routing, shared by the batch calls and their path reports
 namespace {
-// fsg_compress_batch: FSG_PATH_MAIN = the lane-per-message encoder with
-// global-memory tables (v3), when the workspace holds them
-int encode_path(bool have_ws, size_t workspace_bytes, size_t need) {
-  const int forced = g_encode_variant.load(std::memory_order_relaxed);
-  if (forced == 1) return FSG_PATH_FORCED;
-  return have_ws && workspace_bytes >= need ? FSG_PATH_MAIN : FSG_PATH_NO_WORKSPACE;
+// fsg_compress_batch and fsg_compress_report: the call's plan (route, sizes,
+// launches; encode_v3_plan.h) from the current options and kernel selection
+fsg::EncodePlan encode_plan(uint32_t n_msgs, uint32_t max_in_len, size_t workspace_bytes, bool have_ws) {
+  return fsg::encode_v3_plan(n_msgs, max_in_len, workspace_bytes, have_ws,
+                             g_encode_variant.load(std::memory_order_relaxed),
+                             g_region_cap.load(std::memory_order_relaxed), fsg::read_encode_opts());
 }
 // decompress_impl: FSG_PATH_MAIN = the two-pass decoder (v4)
 int decode_path(bool have_ws, size_t workspace_bytes, uint32_t n_msgs, uint32_t flags) {
@@ -313,8 +317,8 @@ int fsg_compress_report(const void* header_host_copy, uint32_t n_msgs, uint32_t 
                         struct fsg_encode_report* out) {
   if (!out) return FSG_ERR_INVALID_ARG;
   *out = fsg_encode_report{};
-  const size_t need = fsg::encode_tables_workspace_bytes(n_msgs, max_in_len, nullptr);
-  out->path = (uint64_t)encode_path(workspace_bytes != 0, workspace_bytes, need);
+  const fsg::EncodePlan p = encode_plan(n_msgs, max_in_len, workspace_bytes, workspace_bytes != 0);
+  out->path = (uint64_t)p.route;
   if (out->path != FSG_PATH_MAIN) {
     out->no_workspace_messages = n_msgs;
     return FSG_SUCCESS;
@@ -328,13 +332,7 @@ int fsg_compress_report(const void* header_host_copy, uint32_t n_msgs, uint32_t 
   out->unit_bytes = c.unit_bytes;
   out->fallback_messages = c.fallback;
   // the wave encoder's share: wave_quota, when the wave encoder ran
-  bool planned = false;
-  if (fsg::encode_v3_wave_min(n_msgs, max_in_len, workspace_bytes, need, encode_wave_min(), &planned)) {
-    fsg::u32 share = 0;
-    fsg::u64 all_bytes = 0;
-    fsg::encode_v3_wave_split(&share, &all_bytes);
-    out->wave_units = fsg::wave_quota_of(c.units, c.unit_bytes, share, all_bytes);
-  }
+  if (p.wave_min) out->wave_units = fsg::wave_quota_of(c.units, c.unit_bytes, p.share_permille, p.all_bytes);
   return FSG_SUCCESS;
 }
 
@@ -389,22 +387,11 @@ int fsg_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off,
   // The lane-per-message encoder with global-memory tables when the
   // workspace allows it (v3: batched speculative probes, the default);
   // otherwise the wave-per-message LDS-table encoder (v1).
-  fsg::u32 slots = 0;
-  const size_t need = fsg::encode_tables_workspace_bytes(n_msgs, max_in_len, &slots);
-  if (encode_path(d_workspace != nullptr, workspace_bytes, need) == FSG_PATH_MAIN) {
-    const fsg::u32 cap = max_in_len == 0 || max_in_len > fsg::kBlockSize ? fsg::kBlockSize : max_in_len;
-    // Lanes in flight: option encode_lanes caps them; otherwise
-    // launch_encode_v3 caps them beside the wave encoder once it knows the
-    // wave encoder runs.
-    const unsigned lanes_cap = (unsigned)fsg::opt(fsg::kOptEncodeLanes);
-    if (lanes_cap && lanes_cap < slots) slots = (lanes_cap + 63) / 64 * 64;
-    return record(fsg::launch_encode_v3(d_in, d_in_off, d_in_len, n_msgs, max_in_len, d_out,
-                                        d_out_off, d_out_len, d_status, d_workspace,
-                                        workspace_bytes, slots, fsg::table_size_for(cap), need,
-                                        g_region_cap.load(std::memory_order_relaxed),
-                                        (hipStream_t)stream, encode_wave_min()),
+  const fsg::EncodePlan p = encode_plan(n_msgs, max_in_len, workspace_bytes, d_workspace != nullptr);
+  if (p.route == fsg::kEncRouteMain)
+    return record(fsg::launch_encode_v3(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_len, d_status,
+                                        d_workspace, (hipStream_t)stream, p),
                   "fsg_compress_batch");
-  }
   return record(fsg::launch_encode(d_in, d_in_off, d_in_len, n_msgs, max_in_len,
                                    d_out, d_out_off, d_out_len, d_status,
                                    (hipStream_t)stream),

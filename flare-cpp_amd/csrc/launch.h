@@ -6,6 +6,7 @@
 #pragma once
 
 #include "decode_v4_plan.h"  // decode_v4_workspace_bytes, decode_v4_bitmap_capacity_words (inline)
+#include "encode_v3_plan.h"
 #include "snappy_device.h"
 
 namespace fsg {
@@ -34,19 +35,14 @@ hipError_t launch_iov_scatter(const u8* in, const u64* in_off, const u32* in_len
                               const u64* iov_len, const u32* iov_first, i32* status, hipStream_t stream);
 
 // ---- Snappy encode
-size_t encode_tables_workspace_bytes(u32 n_msgs, u32 max_in_len, u32* slots_out);
-size_t encode_plan_bytes(u32 n_msgs, u32 max_in_len);
-hipError_t launch_encode_v3(const u8* in, const u64* in_off, const u32* in_len,
-                            u32 n_msgs, u32 max_in_len, u8* out, const u64* out_off,
-                            u32* out_len, i32* status, void* ws, size_t ws_bytes,
-                            u32 slots, u32 entries, size_t tables_bytes, u32 region_cap,
-                            hipStream_t stream, u32 wave_min);
+// (encode_v3_plan.h: encode_tables_workspace_bytes, encode_plan_bytes and encode_v3_plan, inline)
+EncodeOpts read_encode_opts();  // this call's encode options, from the option table
+hipError_t launch_encode_v3(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
+                            const u64* out_off, u32* out_len, i32* status, void* ws, hipStream_t stream,
+                            const EncodePlan& p);
 hipError_t launch_encode(const u8* in, const u64* in_off, const u32* in_len,
                          u32 n_msgs, u32 max_in_len, u8* out, const u64* out_off,
                          u32* out_len, i32* status, hipStream_t stream);
-u32 encode_v3_wave_min(u32 n_msgs, u32 max_in_len, size_t ws_bytes, size_t tables_bytes, u32 wave_min,
-                       bool* planned);
-void encode_v3_wave_split(u32* share_permille, u64* all_bytes);
 
 // ---- gather, pack
 hipError_t launch_gather_blocks(const u64* src, const u32* len, const u64* dst_off, u32 n, u8* dst,

@@ -27,7 +27,7 @@ enum Opt : int {
   kOptExecPrio,           // exec pass priority raise around round-A loads
   kOptExecBigBlocksFork,  // forked path: large-message exec blocks
   kOptExecPack,           // forked path: short bodies per packed execution batch (0 = a wave per body)
-  // Snappy encode (capi.hip, snappy_encode_v3.hip)
+  // Snappy encode (snappy_encode_v3.hip, read_encode_opts; read once per call into EncodeOpts and range-checked in encode_v3_plan.h)
   kOptEncodeWaveMin,      // long-unit threshold of the wave encoder (bytes; 0 = lanes only)
   kOptEncodeWaveShare,    // wave encoder's share of long units (permille)
   kOptEncodeWaveAllMb,    // all long units to the wave encoder below this many MiB

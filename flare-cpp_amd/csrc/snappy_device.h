@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "encode_v3_plan.h"  // kBlockLog .. kInputMarginBytes, table_size_for, kWaveEncMaxWaves, wave_quota_of
+
 namespace fsg {
 
 typedef uint8_t u8;
@@ -15,11 +17,7 @@ typedef uint64_t u64;
 typedef int32_t i32;
 typedef int64_t i64;
 
-constexpr u32 kBlockLog = 16;                    // snappy.h:201
-constexpr u32 kBlockSize = 1u << kBlockLog;      // snappy.h:202
-constexpr u32 kMaxHashTableBits = 14;            // snappy.h:204
-constexpr u32 kMaxHashTableSize = 1u << kMaxHashTableBits;  // snappy.h:205
-constexpr u32 kInputMarginBytes = 15;            // snappy.cc:346
+// (kBlockLog, kBlockSize, kMaxHashTableSize, kInputMarginBytes: encode_v3_plan.h)
 constexpr u32 kHashMul = 0x1e35a7bdu;            // snappy.cc:47
 constexpr int kWave = 64;                        // CDNA wavefront
 
@@ -41,13 +39,6 @@ constexpr i32 kNeedLaneWalk = 0x10000000;
 
 __host__ __device__ inline u64 max_compressed_length(u64 n) {
   return 32 + n + n / 6;  // snappy.cc:55-77
-}
-
-// WorkingMemory::GetHashTable sizing, snappy.cc:247-271.
-__host__ __device__ inline u32 table_size_for(u32 frag_len) {
-  u32 ht = 256;
-  while (ht < kMaxHashTableSize && ht < frag_len) ht <<= 1;
-  return ht;
 }
 
 __host__ __device__ inline int varint32_len(u32 v) {
@@ -85,25 +76,10 @@ __device__ __forceinline__ u32 hash_bytes(u32 bytes, int shift) {
 __device__ __forceinline__ int lane_id() { return __lane_id(); }
 
 // ---- encode work units (encode_plan_kernel's long list)
-constexpr u32 kWaveEncMaxWaves = 5;      // waves per encode_wave_kernel workgroup (at most)
 constexpr u32 kWholeUnit = 0x80000000u;  // unit = a whole message (not a fragment of a split one)
 
 // Units [0, quota) of the long list go to the wave encoder, the rest to the
-// lane encoder.  All of them when their bytes fit what the wave encoder does
-// in about the time one lane needs for a 64 KiB fragment at full load (the
-// lane path's floor: a lane taking a long unit late sets the batch's tail;
-// measured on MI355X: one lane ~40 ms per 64 KiB fragment); otherwise the
-// wave encoder's share of a bandwidth-bound batch (0.5 since round 5: the
-// wave encoder alone does C3 in ~165 ms, the lanes in ~135 ms, and a sweep
-// of 280 / 400 / 500 / 600 permille measured 97-101 / 94 / 87 / 101 ms).
-// Both kernels compute it from the plan pass's counters.
-// (wave_quota_of: the formula on plain values, which the path report
-// evaluates on the host from a copy of the counters.)
-__host__ __device__ __forceinline__ u32 wave_quota_of(u32 n_long, u64 bytes, u32 share_permille, u64 all_bytes) {
-  if (bytes <= all_bytes) return n_long;
-  const u64 q = ((u64)n_long * share_permille + 999) / 1000;
-  return q < n_long ? (u32)q : n_long;
-}
+// lane encoder (wave_quota_of, encode_v3_plan.h), from the plan pass's counters.
 __device__ __forceinline__ u32 wave_quota(const u32* ctr, u32 share_permille, u64 all_bytes) {
   return wave_quota_of(ctr[1], *reinterpret_cast<const unsigned long long*>(ctr + 6), share_permille, all_bytes);
 }

@@ -34,6 +34,7 @@
 // Output bytes equal snappy::Compress(Source*, Sink*) (snappy.cc:875-954);
 // EmitLiteral / EmitCopy follow snappy.cc:156-232.
 #include "launch.h"
+#include "launch_util.h"
 #include "options.h"
 #include "snappy_device.h"
 
@@ -63,22 +64,14 @@ constexpr int kPostFlat = FSG_V3_POST_PROBES;  // probes per batch right after a
 #define FSG_V3_POST_PROBES_SPLIT 2
 #endif
 constexpr u32 kWinChunks = 5;      // 80-byte input window
-// Table entries carry a 16-bit fingerprint of the 4 bytes at the stored
-// position (high half; the position is the low half).  A probe whose
-// fingerprint differs from its candidate's cannot match, so it skips the
-// candidate load: about half of the probes fail, and their candidate lines
-// were a quarter of the fetched bytes.  A fingerprint hit is confirmed by
-// the loaded bytes as before, so the parse is unchanged (FSG_V3_FP=0: the
-// reference's u16 position-only entries).
-#ifndef FSG_V3_FP
-#define FSG_V3_FP 1
-#endif
+// Table entries: position and fingerprint (FSG_V3_FP, encode_v3_plan.h)
 constexpr bool kFp = FSG_V3_FP;
 #if FSG_V3_FP
 typedef u32 tent;
 #else
 typedef u16 tent;
 #endif
+static_assert(sizeof(tent) == kEncEntryBytes, "the workspace is sized for these entries");
 __device__ __forceinline__ u32 fp_of(u32 x) { return (x * 0x9E3779B1u) & 0xffff0000u; }
 __device__ __forceinline__ tent tab_entry(u32 pos, u32 x) { return (tent)(kFp ? pos | fp_of(x) : pos); }
 constexpr u32 kWinDw = kWinChunks * 4;
@@ -514,16 +507,14 @@ __global__ void encode_plan_kernel(const u32* __restrict__ in_len, u32 n_msgs,
   if (long_min) atomicAdd(reinterpret_cast<unsigned long long*>(ctr + 6), (unsigned long long)len);
 }
 
-// Path report (fsg_compress_report): the split messages handed to the
-// whole-message fallback pass, counted where they are marked.  (ctr[] in use:
-// 0 and 4 the lanes' work counters, 1, 2 and 6..7 above, 5 the wave encoder's.)
-constexpr u32 kEncCtrFallback = 8;
+// Path report (fsg_compress_report): the counters (kEncCtr*, encode_v3_plan.h)
+// after a call.
 void encode_v3_header_counts(const void* header, EncodeHeaderCounts* c) {
   u32 ctr[kEncCtrFallback + 1];
   __builtin_memcpy(ctr, header, sizeof(ctr));
-  c->units = ctr[1];
-  c->split = ctr[2];
-  c->unit_bytes = ctr[6] | (u64)ctr[7] << 32;
+  c->units = ctr[kEncCtrUnits];
+  c->split = ctr[kEncCtrSplit];
+  c->unit_bytes = ctr[kEncCtrUnitBytes] | (u64)ctr[kEncCtrUnitBytes + 1] << 32;
   c->fallback = ctr[kEncCtrFallback];
 }
 
@@ -593,73 +584,6 @@ __global__ __launch_bounds__(256) void encode_gather_kernel(
   }
 }
 
-// Per-lane hash tables for the lane-per-message encoder: [counter: 256 B]
-// [tables: slots x entries x sizeof(tent)] (tent = u32 with FSG_V3_FP, the
-// default: position + fingerprint, twice the u16 footprint), entries per WorkingMemory::GetHashTable
-// (snappy.cc:247-271) for the largest fragment of the batch.
-size_t encode_tables_workspace_bytes(u32 n_msgs, u32 max_in_len, u32* slots_out) {
-  u32 cap = max_in_len == 0 || max_in_len > kBlockSize ? kBlockSize : max_in_len;
-  const u32 entries = table_size_for(cap);
-  // enough lanes to fill the chip several times over: 256 CUs x 16 waves x 64
-  u32 slots = n_msgs < 262144u ? n_msgs : 262144u;
-  slots = (slots + 255) / 256 * 256;
-  if (slots == 0) slots = 256;
-  if (slots_out) *slots_out = slots;
-  return 256 + (size_t)slots * entries * sizeof(tent);
-}
-
-// Plan region: units (2 x u32 each: message, fragment or kWholeUnit), per-unit
-// sizes, per-message first unit, split-message list.  Present when a message
-// may be split (max_in_len > 64 KiB) or may be long enough for the wave
-// encoder (>= kWaveMinBound).  (max_in_len 0 = unknown: no plan, every
-// message encoded whole by one lane.)
-constexpr u32 kWaveMinBound = 4096;  // smallest wave_min the plan region is sized for
-constexpr u32 kSmallBatchEnc = 64;   // batches of at most this many messages: every message on the wave encoder
-// Batches of short bodies only (at most this many bytes each): every message
-// on the wave encoder too.  Their tables are small (8 KiB for 4 KiB bodies),
-// so many waves fit per CU, and nothing else in the batch needs the LDS:
-// 131,072 x 4 KiB text 19.1 -> 8.6 ms, 65,536 x 8 KiB 18.5 -> 11.4 ms
-// against the lanes.
-#ifndef FSG_ENC_ALL_WAVE_MAX
-#define FSG_ENC_ALL_WAVE_MAX 8192
-#endif
-constexpr u32 kAllWaveMax = FSG_ENC_ALL_WAVE_MAX;
-__host__ __device__ inline bool all_on_wave(u32 n_msgs, u32 max_in_len) {
-  return max_in_len >= kInputMarginBytes && (n_msgs <= kSmallBatchEnc || max_in_len <= kAllWaveMax);
-}
-size_t encode_plan_bytes(u32 n_msgs, u32 max_in_len) {
-  if (max_in_len < kWaveMinBound && !all_on_wave(n_msgs, max_in_len)) return 0;
-  u64 per_msg = ((u64)max_in_len + kBlockSize - 1) >> kBlockLog;
-  if (per_msg < 1) per_msg = 1;
-  const u64 max_items = (u64)n_msgs * per_msg;
-  return (size_t)(max_items * 12 + (u64)n_msgs * 8 + 256);
-}
-
-// The wave encoder's lower bound on a unit's bytes for this call (0: the wave
-// encoder does not run), and whether the plan pass runs.  Shared by the
-// launch and the path report.
-u32 encode_v3_wave_min(u32 n_msgs, u32 max_in_len, size_t ws_bytes, size_t tables_bytes, u32 wave_min,
-                       bool* planned) {
-  const size_t plan = encode_plan_bytes(n_msgs, max_in_len);
-  const bool can_split = max_in_len > kBlockSize;
-  if (wave_min && wave_min < kWaveMinBound) wave_min = kWaveMinBound;
-  // A batch of at most one wave of messages (the host runtime's one-caller
-  // batches: the wave encoder's latency for one message is a fraction of one
-  // lane's, 4 KiB text ~0.2 ms against 1.1 ms in the C1 echo trace), or of
-  // short bodies only (kAllWaveMax): every message on the wave encoder
-  if (wave_min && all_on_wave(n_msgs, max_in_len)) wave_min = kInputMarginBytes;
-  if (max_in_len < wave_min) wave_min = 0;  // nothing long enough (or no bound known)
-  *planned = plan && ws_bytes >= tables_bytes + plan && (can_split || wave_min);
-  return *planned ? wave_min : 0u;
-}
-
-// wave_quota's parameters from options encode_wave_share / encode_wave_all_mb
-void encode_v3_wave_split(u32* share_permille, u64* all_bytes) {
-  const i64 share_opt = opt(kOptEncodeWaveShare), all_opt = opt(kOptEncodeWaveAllMb);
-  *share_permille = share_opt >= 0 && share_opt <= 1000 ? (u32)share_opt : 475u;
-  *all_bytes = (all_opt >= 0 && all_opt < (1 << 24) ? (u64)all_opt : 640ull) << 20;
-}
-
 __global__ void encode_wave_kernel(const u8* __restrict__ in, const u64* __restrict__ in_off,
                                    const u32* __restrict__ in_len, u32 n_msgs, u8* out,
                                    const u64* __restrict__ out_off, u32* __restrict__ out_len,
@@ -675,110 +599,54 @@ struct EncSide {
   hipEvent_t fork = nullptr, join = nullptr;
   std::mutex mu;
 };
-EncSide* enc_side() {
-  constexpr int kMaxDevices = 64;
-  static EncSide g[kMaxDevices];
-  static std::once_flag once[kMaxDevices];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
-  EncSide* s = &g[dev];
-  std::call_once(once[dev], [s] {
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&s->fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s->join, hipEventDisableTiming) != hipSuccess)
-      s->stream = nullptr;
-  });
-  return s->stream ? s : nullptr;
+bool create_enc_side(EncSide* s) {
+  return hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) == hipSuccess &&
+         hipEventCreateWithFlags(&s->fork, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&s->join, hipEventDisableTiming) == hipSuccess;
 }
 }  // namespace
 
-hipError_t launch_encode_v3(const u8* in, const u64* in_off, const u32* in_len,
-                            u32 n_msgs, u32 max_in_len, u8* out, const u64* out_off,
-                            u32* out_len, i32* status, void* ws, size_t ws_bytes,
-                            u32 slots, u32 entries, size_t tables_bytes, u32 region_cap,
-                            hipStream_t stream, u32 wave_min) {
+// This call's options (csrc/options.h, set with fsg_set_option; never the
+// environment here).
+EncodeOpts read_encode_opts() {
+  EncodeOpts o;
+  o.encode_wave_min = opt(kOptEncodeWaveMin);
+  o.encode_wave_share = opt(kOptEncodeWaveShare);
+  o.encode_wave_all_mb = opt(kOptEncodeWaveAllMb);
+  o.encode_lanes = opt(kOptEncodeLanes);
+  o.encode_wave_per_cu = opt(kOptEncodeWavePerCu);
+  o.encode_wave_wg = opt(kOptEncodeWaveWg);
+  return o;
+}
+
+// fill, plan kernel, fork, wave kernel, lanes, join, gather, fallback: every
+// size and decision from encode_v3_plan (p.route is the main one).
+hipError_t launch_encode_v3(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
+                            const u64* out_off, u32* out_len, i32* status, void* ws, hipStream_t stream,
+                            const EncodePlan& p) {
   if (n_msgs == 0) return hipSuccess;
+  u8* const base = reinterpret_cast<u8*>(ws);
   u32* ctr = reinterpret_cast<u32*>(ws);
-  tent* tables = reinterpret_cast<tent*>(reinterpret_cast<u8*>(ws) + 256);
-  hipError_t e = hipMemsetAsync(ctr, 0, 256, stream);
+  tent* tables = reinterpret_cast<tent*>(base + kEncCounterBytes);
+  hipError_t e = hipMemsetAsync(ctr, 0, kEncCounterBytes, stream);
   if (e != hipSuccess) return e;
-  const size_t plan = encode_plan_bytes(n_msgs, max_in_len);
   u32 *items = nullptr, *sizes = nullptr, *frag_base = nullptr, *big_list = nullptr;
-  const bool can_split = max_in_len > kBlockSize;
-  bool planned = false;
-  wave_min = encode_v3_wave_min(n_msgs, max_in_len, ws_bytes, tables_bytes, wave_min, &planned);
-  if (planned) {
-    const u64 max_items = (plan - 256 - (u64)n_msgs * 8) / 12;
-    u8* p = reinterpret_cast<u8*>(ws) + tables_bytes;
-    items = reinterpret_cast<u32*>(p);
-    sizes = items + 2 * max_items;
-    frag_base = sizes + max_items;
-    big_list = frag_base + n_msgs;
-    encode_plan_kernel<<<(n_msgs + 255) / 256, 256, 0, stream>>>(in_len, n_msgs, ctr, items, frag_base, big_list,
-                                                                 wave_min);
+  if (p.planned) {
+    items = reinterpret_cast<u32*>(base + p.items_off);
+    sizes = reinterpret_cast<u32*>(base + p.sizes_off);
+    frag_base = reinterpret_cast<u32*>(base + p.frag_base_off);
+    big_list = reinterpret_cast<u32*>(base + p.big_list_off);
+    encode_plan_kernel<<<p.plan_pass.grid, p.plan_pass.block, 0, stream>>>(in_len, n_msgs, ctr, items, frag_base,
+                                                                         big_list, p.wave_min);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  // Lanes in flight beside the wave encoder (decided here, once it is known
-  // to run): 3/4 of the messages, at most 131,072.  The lanes' waves share
-  // the SIMDs with the wave encoder's waves, whose serial chains set the
-  // batch's time, and fewer lanes keep their tables and recent input
-  // cache-resident, each encoding more messages.  Measured (A/B, one box): C5
-  // 27.0 -> 18.8 ms (131,072 of 262,144; 98,304: 20.8, 196,608: 22.4), C3
-  // 92.3 -> 85.4 ms (49,152 of 65,536; 32,768: 85.3).  Option encode_lanes
-  // (a cap applied by the caller) replaces this rule.
-  if (wave_min && n_msgs > 64 && opt(kOptEncodeLanes) == 0) {
-    u32 beside = (u32)(((u64)n_msgs * 3 / 4 + 255) / 256 * 256);
-    if (beside > 131072u) beside = 131072u;
-    if (beside < slots) slots = beside;
-  }
-  // (options encode_wave_share / encode_wave_all_mb: the tests force the lane
-  // share with encode_wave_all_mb 0).  The wave encoder's share of the long
-  // units' bytes above the all-on-wave bound, in permille: C3, A/B on one box
-  // (profiles/r6/enc/ab_c3_share_sweep*.log), 400 86.3-86.9 ms, 425 80.8-81.0,
-  // 450 80.4-80.6, 475 80.2-80.3, 500 82.4-82.6, 550 89.6-90.1.
-  u32 kShare = 0;
-  u64 kAllBytes = 0;
-  encode_v3_wave_split(&kShare, &kAllBytes);
-  auto pipe = max_in_len > kBlockSize || max_in_len == 0
-                  ? encode_pipe_kernel<FSG_V3_PROBES_SPLIT, FSG_V3_POST_PROBES_SPLIT>
-                  : encode_pipe_kernel<kKFlat, kPostFlat>;
-  // The wave encoder's share of the long units (hash table in LDS, one wave
-  // per fragment: snappy_encode_wave.hip) runs on a side stream beside the
-  // lanes, one wave per table's worth of LDS.
-  EncSide* side = wave_min ? enc_side() : nullptr;
+  auto pipe = p.split_pipe ? encode_pipe_kernel<FSG_V3_PROBES_SPLIT, FSG_V3_POST_PROBES_SPLIT>
+                           : encode_pipe_kernel<kKFlat, kPostFlat>;
+  // The wave encoder's share of the long units runs on a side stream beside
+  // the lanes.
+  EncSide* side = p.wave_min ? per_device<EncSide>(create_enc_side) : nullptr;
   std::unique_lock<std::mutex> lk;
-  if (wave_min) {
-    const u32 cap = max_in_len > kBlockSize ? kBlockSize : max_in_len;
-    const u32 ht = table_size_for(cap), lds = ht * 2;
-    // Workgroups of wg waves, one table each in the workgroup's LDS.  LDS is
-    // allocated per workgroup in 1,280-byte granules out of 163,840 per CU
-    // (profiles/r5/wenc/lds_resident_probe.txt: one-wave workgroups of
-    // 31,744 B fit five per CU, of 32,256 B four), so five 32 KiB tables fit
-    // only as one five-wave workgroup.
-    constexpr u32 kCuLds = 160u * 1024u, kLdsGranule = 1280u;
-    // Waves per workgroup (option encode_wave_wg, 1..5; default 1).  Five
-    // 32 KiB tables fit per CU only as one five-wave workgroup, which takes
-    // the CU's whole LDS: C3 with every unit on the wave encoder 159 -> 132
-    // ms, but beside the lanes (whose 80-byte LDS windows then find no room)
-    // C3 gained <= 1% and C5 lost 12% with the lanes' windows moved to
-    // registers, and batches of short bodies alone lost 33-60% (DESIGN.md
-    // section 5, round 6).
-    const i64 wg_opt = opt(kOptEncodeWaveWg);
-    u32 wg = wg_opt >= 1 && wg_opt <= (i64)kWaveEncMaxWaves ? (u32)wg_opt : 1u;
-    while (wg > 1 && wg * lds > kCuLds) --wg;
-    const u32 alloc = (wg * lds + kLdsGranule - 1) / kLdsGranule * kLdsGranule;
-    u32 per_cu = (kCuLds / alloc) * wg;
-    if (per_cu > 32) per_cu = 32;  // waves per CU
-    const i64 pc_opt = opt(kOptEncodeWavePerCu);
-    if (pc_opt > 0 && (u64)pc_opt < per_cu) per_cu = (u32)pc_opt;
-    u32 waves = 256u * (per_cu ? per_cu : 1u);
-    // A batch has at most n_msgs x fragments units; the waves past them find
-    // no unit but are still dispatched (one 4 KiB body: 5,120 waves of 8 KiB
-    // tables, ~60 us in front of the lanes' launch).
-    {
-      const u64 units = (u64)n_msgs * (((u64)max_in_len + kBlockSize - 1) >> kBlockLog);
-      if (units && units < waves) waves = (u32)units;
-    }
+  if (p.wave_min) {
     hipStream_t wstream = stream;
     if (side) {
       lk = std::unique_lock<std::mutex>(side->mu);
@@ -786,23 +654,24 @@ hipError_t launch_encode_v3(const u8* in, const u64* in_off, const u32* in_len,
       if ((e = hipStreamWaitEvent(side->stream, side->fork, 0)) != hipSuccess) return e;
       wstream = side->stream;
     }
-    if (wg > waves) wg = waves;
-    encode_wave_kernel<<<(waves + wg - 1) / wg, 64 * wg, wg * lds, wstream>>>(
-        in, in_off, in_len, n_msgs, out, out_off, out_len, status, ctr, items, sizes, region_cap, kShare, kAllBytes, ht);
+    encode_wave_kernel<<<p.wave.grid, p.wave.block, p.wave.lds, wstream>>>(
+        in, in_off, in_len, n_msgs, out, out_off, out_len, status, ctr, items, sizes, p.region_cap, p.share_permille,
+        p.all_bytes, p.ht);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (side && (e = hipEventRecord(side->join, side->stream)) != hipSuccess) return e;
   }
-  pipe<<<slots / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_len, status, tables, entries,
-                                      ctr, items, sizes, 0u, region_cap, wave_min, kShare, kAllBytes);
+  pipe<<<p.pipe.grid, p.pipe.block, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_len, status, tables,
+                                                 p.entries, ctr, items, sizes, 0u, p.region_cap, p.wave_min,
+                                                 p.share_permille, p.all_bytes);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (side && (e = hipStreamWaitEvent(stream, side->join, 0)) != hipSuccess) return e;
   if (lk.owns_lock()) lk.unlock();
-  if (items && can_split) {
-    encode_gather_kernel<<<1024, 256, 0, stream>>>(in_len, out, out_off, out_len, status, ctr,
-                                                   frag_base, big_list, sizes, region_cap);
+  if (p.fallback) {
+    encode_gather_kernel<<<p.gather.grid, p.gather.block, 0, stream>>>(in_len, out, out_off, out_len, status, ctr,
+                                                                     frag_base, big_list, sizes, p.region_cap);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    pipe<<<slots / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_len, status,
-                                        tables, entries, ctr, nullptr, nullptr, kEncFallback, 0u, 0u, 0u, 0ull);
+    pipe<<<p.pipe.grid, p.pipe.block, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_len, status, tables,
+                                                   p.entries, ctr, nullptr, nullptr, kEncFallback, 0u, 0u, 0u, 0ull);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   return hipSuccess;

@@ -749,7 +749,7 @@ def test_wave_encoder_against_oracle(gpu, oracle, wave_min, all_mb, fsg_opts):
 
 def test_small_batch_wave_encoder(gpu, oracle):
     """Batches of <= 64 messages put every message of >= 15 bytes on the wave
-    encoder (snappy_encode_v3.hip kSmallBatchEnc).  Batches of 1, 7 and 64
+    encoder (encode_v3_plan.h kSmallBatchEnc).  Batches of 1, 7 and 64
     messages over golden inputs, random alphabets, periodic data, long runs,
     split messages and the input-margin edge sizes: bytes equal the
     oracle's."""
