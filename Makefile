@@ -6,8 +6,8 @@ PKG      := flare-cpp_amd
 LIB      := $(PKG)/lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall
 CSRC     := $(PKG)/csrc/capi.hip $(PKG)/csrc/snappy_decode.hip $(PKG)/csrc/snappy_decode_v3.hip $(PKG)/csrc/snappy_decode_v4.hip $(PKG)/csrc/snappy_decode_partial.hip \
-            $(PKG)/csrc/snappy_encode.hip $(PKG)/csrc/snappy_encode_v3.hip $(PKG)/csrc/snappy_encode_wave.hip $(PKG)/csrc/gather.hip $(PKG)/csrc/pack.hip $(PKG)/csrc/lz4.hip $(PKG)/csrc/lz4_decode2.hip $(PKG)/csrc/lz4_encode_wave.hip $(PKG)/csrc/lz4_frame.hip $(PKG)/csrc/inflate.hip $(PKG)/csrc/deflate.hip $(PKG)/csrc/deflate_level.hip
-CHDRS    := $(wildcard $(PKG)/csrc/*.h) include/flare_snappy_gpu.h include/flare_lz4_gpu.h include/flare_deflate_gpu.h include/flare_deflate_compress_gpu.h include/flare_deflate_level_gpu.h
+            $(PKG)/csrc/snappy_encode.hip $(PKG)/csrc/snappy_encode_v3.hip $(PKG)/csrc/snappy_encode_wave.hip $(PKG)/csrc/gather.hip $(PKG)/csrc/pack.hip $(PKG)/csrc/lz4.hip $(PKG)/csrc/lz4_decode2.hip $(PKG)/csrc/lz4_encode_wave.hip $(PKG)/csrc/lz4_frame.hip $(PKG)/csrc/inflate.hip $(PKG)/csrc/inflate_units.hip $(PKG)/csrc/deflate.hip $(PKG)/csrc/deflate_level.hip
+CHDRS    := $(wildcard $(PKG)/csrc/*.h) include/flare_snappy_gpu.h include/flare_lz4_gpu.h include/flare_deflate_gpu.h include/flare_deflate_compress_gpu.h include/flare_deflate_level_gpu.h include/flare_deflate_index_gpu.h
 OBJDIR   := build/obj
 
 all: gpu host datagen oracle cpptests hostbench echobench
@@ -26,7 +26,7 @@ $(LIB)/libflare_snappy_gpu.so: $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/%.o,$(CSRC
 # handler + flat API): host-only code built with g++ against the HIP runtime.
 HOSTCXX   := g++ -std=c++17 -O2 -fPIC -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 HOST_SRC  := $(wildcard $(PKG)/host/*.cc)
-HOST_HDRS := $(wildcard $(PKG)/host/*.h) include/flare_snappy_gpu.h $(PKG)/csrc/lz4_frame_format.h $(PKG)/csrc/inflate_format.h $(PKG)/csrc/deflate_format.h
+HOST_HDRS := $(wildcard $(PKG)/host/*.h) include/flare_snappy_gpu.h $(PKG)/csrc/lz4_frame_format.h $(PKG)/csrc/inflate_format.h $(PKG)/csrc/deflate_format.h $(PKG)/csrc/gzip_index.h
 host: $(LIB)/libflare_rpc_snappy.so
 
 $(LIB)/libflare_rpc_snappy.so: $(HOST_SRC) $(HOST_HDRS) $(LIB)/libflare_snappy_gpu.so
@@ -36,7 +36,7 @@ $(LIB)/libflare_rpc_snappy.so: $(HOST_SRC) $(HOST_HDRS) $(LIB)/libflare_snappy_g
 
 # C++ tests mirroring test/rpc/rpc_snappy_compress_test.cc and the baidu_std /
 # rpc_dump framing (run by pytest)
-cpptests: build/test_rpc_snappy_compress build/test_baidu_std build/test_pack_output build/test_path_report build/test_lz4_frame_handler build/test_gzip_handler build/test_gzip_options
+cpptests: build/test_rpc_snappy_compress build/test_baidu_std build/test_pack_output build/test_path_report build/test_lz4_frame_handler build/test_gzip_handler build/test_gzip_options build/test_gzip_unit_index
 
 # the LZ4 frame CompressHandler (policy::Lz4FrameCompress / Lz4FrameDecompress), host only
 build/test_lz4_frame_handler: tests/cpp/test_lz4_frame_handler.cc $(HOST_HDRS) $(LIB)/libflare_rpc_snappy.so
@@ -54,6 +54,13 @@ build/test_gzip_handler: tests/cpp/test_gzip_handler.cc $(HOST_HDRS) $(LIB)/libf
 
 # GzipCompress with GzipCompressOptions (format and compression level), host only
 build/test_gzip_options: tests/cpp/test_gzip_options.cc $(HOST_HDRS) $(LIB)/libflare_rpc_snappy.so
+	@mkdir -p build
+	$(HOSTCXX) -o $@ $< -I$(PKG)/host -L$(LIB) -lflare_rpc_snappy -lflare_snappy_gpu \
+	  -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$(abspath $(LIB)) -Wl,-rpath,'$$ORIGIN/../$(LIB)' \
+	  -Wl,-rpath,/opt/rocm/lib -pthread
+
+# GzipCompressOptions::unit_index (gzip bodies that carry their units' lengths), host only
+build/test_gzip_unit_index: tests/cpp/test_gzip_unit_index.cc $(HOST_HDRS) $(LIB)/libflare_rpc_snappy.so
 	@mkdir -p build
 	$(HOSTCXX) -o $@ $< -I$(PKG)/host -L$(LIB) -lflare_rpc_snappy -lflare_snappy_gpu \
 	  -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$(abspath $(LIB)) -Wl,-rpath,'$$ORIGIN/../$(LIB)' \

@@ -7,10 +7,12 @@
 #include <cstring>
 
 #include "../../include/flare_deflate_gpu.h"
+#include "../../include/flare_deflate_index_gpu.h"
 #include "../../include/flare_deflate_level_gpu.h"
 #include "../../include/flare_lz4_gpu.h"
 #include "../../include/flare_snappy_gpu.h"
 #include "deflate_format.h"
+#include "gzip_index.h"
 #include "launch.h"
 #include "launch_util.h"
 #include "options.h"
@@ -733,16 +735,89 @@ int fsg_deflate_batch_level(const uint8_t* d_in, const uint64_t* d_in_off, const
                             uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status,
                             uint32_t format, uint32_t level, void* d_workspace, size_t workspace_bytes,
                             void* stream) {
+  return fsg_deflate_batch_flags(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_len, d_status, format,
+                                 level, 0, d_workspace, workspace_bytes, stream);
+}
+
+// ---- the unit index (include/flare_deflate_index_gpu.h)
+static bool deflate_flags_ok(uint32_t format, uint32_t flags) {
+  return !(flags & ~FSG_DEFLATE_FLAG_UNIT_INDEX) && (flags == 0 || format == FSG_DEFLATE_GZIP);
+}
+
+size_t fsg_deflate_max_length_flags(size_t n, uint32_t format, uint32_t flags) {
+  if (format > FSG_DEFLATE_GZIP || !deflate_flags_ok(format, flags)) return 0;
+  const uint64_t units = defl::unit_count(n);
+  return (size_t)(defl::max_length(n, format) +
+                  (gzidx::writes_index(format, flags, units) ? gzidx::head_bytes((uint32_t)units) - 10 : 0));
+}
+
+int fsg_deflate_batch_flags(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_msgs,
+                            uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status,
+                            uint32_t format, uint32_t level, uint32_t flags, void* d_workspace,
+                            size_t workspace_bytes, void* stream) {
   if (level > FSG_DEFLATE_LEVEL_BEST) return FSG_ERR_INVALID_ARG;
   if (format > FSG_DEFLATE_GZIP) return FSG_ERR_INVALID_ARG;
+  if (!deflate_flags_ok(format, flags)) return FSG_ERR_INVALID_ARG;
   if (n_msgs == 0) return FSG_SUCCESS;
   if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len || !d_status || !d_workspace)
     return FSG_ERR_INVALID_ARG;
   if (reinterpret_cast<uintptr_t>(d_workspace) & 15u) return FSG_ERR_INVALID_ARG;
   if (fsg::deflate_unit_capacity(n_msgs, workspace_bytes) == 0) return FSG_ERR_INVALID_ARG;
   return record(fsg::launch_deflate(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_len, d_status, format,
-                                    level, d_workspace, workspace_bytes, (hipStream_t)stream),
+                                    level, flags, d_workspace, workspace_bytes, (hipStream_t)stream),
                 "fsg_deflate_batch");
+}
+
+size_t fsg_inflate_units_workspace_bytes(uint32_t n_msgs, uint64_t extra_units) {
+  return fsg::inflate_units_workspace_bytes(n_msgs, extra_units);
+}
+
+static bool inflate_units_ws_ok(uint32_t n_msgs, const void* d_workspace, size_t workspace_bytes) {
+  return d_workspace && !(reinterpret_cast<uintptr_t>(d_workspace) & 15u) &&
+         fsg::inflate_units_entry_capacity(n_msgs, workspace_bytes) != 0;
+}
+
+int fsg_inflate_units_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_msgs,
+                            uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_cap,
+                            uint32_t* d_out_len, int32_t* d_status, uint32_t format, void* d_workspace,
+                            size_t workspace_bytes, void* stream) {
+  if (format > FSG_INFLATE_GZIP) return FSG_ERR_INVALID_ARG;
+  if (n_msgs == 0) return FSG_SUCCESS;
+  if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status)
+    return FSG_ERR_INVALID_ARG;
+  if (!inflate_units_ws_ok(n_msgs, d_workspace, workspace_bytes)) return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_inflate_units(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
+                                          d_status, format, d_workspace, workspace_bytes, (hipStream_t)stream),
+                "fsg_inflate_units_batch");
+}
+
+int fsg_inflate_units_lengths_batch(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                    uint32_t n_msgs, uint64_t* d_length, int32_t* d_status, uint32_t format,
+                                    void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (format > FSG_INFLATE_GZIP) return FSG_ERR_INVALID_ARG;
+  if (n_msgs == 0) return FSG_SUCCESS;
+  if (!d_in || !d_in_off || !d_in_len || !d_length || !d_status) return FSG_ERR_INVALID_ARG;
+  if (!inflate_units_ws_ok(n_msgs, d_workspace, workspace_bytes)) return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_inflate_units_lengths(d_in, d_in_off, d_in_len, n_msgs, d_length, d_status, format,
+                                                  d_workspace, workspace_bytes, (hipStream_t)stream),
+                "fsg_inflate_units_lengths_batch");
+}
+
+int fsg_inflate_units_report(const void* header_host_copy, uint32_t n_msgs, size_t workspace_bytes,
+                             struct fsg_inflate_units_report* out) {
+  if (!header_host_copy || !out) return FSG_ERR_INVALID_ARG;
+  const uint64_t cap = fsg::inflate_units_entry_capacity(n_msgs, workspace_bytes);
+  if (n_msgs && cap == 0) return FSG_ERR_INVALID_ARG;
+  fsg::InflateUnitsHeaderCounts c;
+  fsg::inflate_units_header_counts(header_host_copy, &c);
+  out->parallel_messages = c.parallel_bodies;
+  out->parallel_units = c.parallel_units;
+  out->serial_no_index = c.no_index;
+  out->serial_unusable_index = c.unusable;
+  out->serial_unit_mismatch = c.mismatch;
+  out->serial_workspace = c.overflow;
+  out->unit_entries = cap;
+  return FSG_SUCCESS;
 }
 
 int fsg_deflate_report(const void* header_host_copy, uint32_t n_msgs, size_t workspace_bytes,

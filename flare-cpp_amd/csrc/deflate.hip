@@ -21,7 +21,11 @@
 //             unit is a cooperative copy.
 //   checksum  inflate_sum.h's kernel over the input bodies (zlib, gzip only)
 //   assemble  a wave per body: the units' places, wrapper head and trailer,
-//             d_out_len, d_status; then a wave per unit copies its bytes
+//             d_out_len, d_status; then a wave per unit copies its bytes.
+//             With FSG_DEFLATE_FLAG_UNIT_INDEX (fsg_deflate_batch_flags,
+//             include/flare_deflate_index_gpu.h) a gzip body's head is
+//             gzip_index.h's, 22 + 2 * units bytes: its length follows from
+//             the unit count, its size entries are the units' lengths
 // No wave waits on another wave.
 //
 // The unit kernel is deflate_unit.h's, a template over the level
@@ -29,6 +33,7 @@
 // launched here, levels 0 and 2 by deflate_level.hip; every other launch is
 // the same at all levels.
 #include "deflate_unit.h"
+#include "gzip_index.h"
 
 namespace fsg {
 
@@ -142,13 +147,16 @@ __global__ __launch_bounds__(64) void deflate_list_kernel(const u32* __restrict_
 // ---- assemble.  A wave per body (grid stride): where each unit's bytes go,
 // the wrapper, the result columns.
 __global__ __launch_bounds__(64) void deflate_place_kernel(const u32* __restrict__ in_len, u32 n_msgs, u32 format,
-                                                           Cols c, u32* units, u8* out,
+                                                           u32 flags, Cols c, u32* units, u8* out,
                                                            const u64* __restrict__ out_off, u32* __restrict__ out_len,
                                                            i32* __restrict__ status) {
   const u32 lane = threadIdx.x;
-  const u32 head = defl::wrapper_head(format), tail = defl::wrapper_tail(format);
+  const u32 tail = defl::wrapper_tail(format);
   for (u32 m = blockIdx.x; m < n_msgs; m += gridDim.x) {
     const u32 cnt = rfl(c.ucount[m]), ub = rfl(c.ubase[m]);
+    const bool index = gzidx::writes_index(format, flags, cnt);
+    const u32 head = index ? gzidx::head_bytes(cnt) : defl::wrapper_head(format);
+    u8* const d = out + out_off[m];
     u64 run = 0;
     bool broken = cnt == 0;
     for (u32 k0 = 0; k0 < cnt; k0 += 64) {
@@ -164,15 +172,19 @@ __global__ __launch_bounds__(64) void deflate_place_kernel(const u32* __restrict
       }
       run += readlane(incl, 63);
     }
+    if (index && !broken)  // the size entries, behind the head's first 22 bytes
+      for (u32 k = lane; k < cnt; k += 64) gzidx::wr16(d + 22 + 2 * k, units[(size_t)(ub + k) * kUnitWords + kUOutLen]);
     if (lane == 0) {
       if (broken) {
         out_len[m] = 0;
         status[m] = kCorrupt;
       } else {
-        u8* d = out + out_off[m];
-        u8 w[10];
-        defl::write_wrapper_head(format, w);
-        for (u32 k = 0; k < head; ++k) d[k] = w[k];
+        u8 w[22];
+        if (index)
+          gzidx::write_head(cnt, defl::kUnit, w);
+        else
+          defl::write_wrapper_head(format, w);
+        for (u32 k = 0; k < (index ? 22u : head); ++k) d[k] = w[k];
         defl::write_wrapper_tail(format, c.sum[m], in_len[m], w);
         for (u32 k = 0; k < tail; ++k) d[head + run + k] = w[k];
         out_len[m] = (u32)(head + run + tail);
@@ -184,14 +196,16 @@ __global__ __launch_bounds__(64) void deflate_place_kernel(const u32* __restrict
 
 // A wave per unit (grid stride): the staged bytes to their place in the slot.
 __global__ __launch_bounds__(64) void deflate_copy_kernel(const u32* hdr, const u32* __restrict__ units, u32 format,
+                                                          u32 flags, const u32* __restrict__ ucount,
                                                           const u8* __restrict__ stage_base, u8* out,
                                                           const u64* __restrict__ out_off) {
   const u32 lane = threadIdx.x;
-  const u32 total = rfl(hdr[kHdrUnits]), head = defl::wrapper_head(format);
+  const u32 total = rfl(hdr[kHdrUnits]);
   for (u32 ui = blockIdx.x; ui < total; ui += gridDim.x) {
     const u32* e = units + (size_t)ui * kUnitWords;
     if (rfl(e[kUType]) == kBroken) continue;
-    const u32 len = rfl(e[kUOutLen]);
+    const u32 len = rfl(e[kUOutLen]), cnt = rfl(ucount[rfl(e[kUBody])]);
+    const u32 head = gzidx::writes_index(format, flags, cnt) ? gzidx::head_bytes(cnt) : defl::wrapper_head(format);
     const u8* s = stage_base + ((u64)rfl(e[kUStageHi]) << 32 | rfl(e[kUStageLo])) * 16;
     u8* d = out + rfl64(out_off[rfl(e[kUBody])]) + head + ((u64)rfl(e[kUPosHi]) << 32 | rfl(e[kUPosLo]));
     for (u32 k = lane; k < (len >> 4); k += 64) copy16(d + 16 * k, s + 16 * k);
@@ -227,7 +241,7 @@ u64 deflate_unit_capacity(u32 n_msgs, size_t ws_bytes) {
 }
 
 hipError_t launch_deflate(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out, const u64* out_off,
-                          u32* out_len, i32* status, u32 format, u32 level, void* ws_, size_t ws_bytes,
+                          u32* out_len, i32* status, u32 format, u32 level, u32 flags, void* ws_, size_t ws_bytes,
                           hipStream_t stream) {
   if (level > defl::kMaxLevel) return hipErrorInvalidValue;
   if (n_msgs == 0) return hipSuccess;
@@ -256,10 +270,11 @@ hipError_t launch_deflate(const u8* in, const u64* in_off, const u32* in_len, u3
     e = launch_inflate_sum(in, in_off, in_len, n_msgs, c.sum, format == defl::kZlib, stream);
     if (e != hipSuccess) return e;
   }
-  deflate_place_kernel<<<body_grid, 64, 0, stream>>>(in_len, n_msgs, format, c, units, out, out_off, out_len, status);
+  deflate_place_kernel<<<body_grid, 64, 0, stream>>>(in_len, n_msgs, format, flags, c, units, out, out_off, out_len,
+                                                     status);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  deflate_copy_kernel<<<p.cap_units < 65536 ? p.cap_units : 65536, 64, 0, stream>>>(hdr, units, format, stage, out,
-                                                                                  out_off);
+  deflate_copy_kernel<<<p.cap_units < 65536 ? p.cap_units : 65536, 64, 0, stream>>>(hdr, units, format, flags,
+                                                                                  c.ucount, stage, out, out_off);
   return hipGetLastError();
 }
 

@@ -129,14 +129,35 @@ hipError_t launch_inflate_lengths(const u8* in, const u64* in_off, const u32* in
 hipError_t launch_inflate_sum(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u32* sum, bool adler,
                               hipStream_t stream);
 
+// the trailer judge behind a decode kernel: zlib or gzip bodies left FSG_OK (n_msgs > 0)
+hipError_t launch_inflate_judge(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, const u8* out,
+                                const u64* out_off, u32* out_len, i32* status, u32 format, hipStream_t stream);
+
+// ---- inflate by units (inflate_units.hip; include/flare_deflate_index_gpu.h): a
+// wave per unit of the gzip bodies that carry a unit index.
+// inflate_units_entry_capacity: the unit entries a workspace holds (0: below
+// inflate_units_workspace_bytes(n_msgs, 0)).
+size_t inflate_units_workspace_bytes(u32 n_msgs, u64 extra_units);
+u64 inflate_units_entry_capacity(u32 n_msgs, size_t ws_bytes);
+hipError_t launch_inflate_units(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
+                                const u64* out_off, const u32* out_cap, u32* out_len, i32* status, u32 format,
+                                void* ws, size_t ws_bytes, hipStream_t stream);
+hipError_t launch_inflate_units_lengths(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* lengths,
+                                        i32* status, u32 format, void* ws, size_t ws_bytes, hipStream_t stream);
+struct InflateUnitsHeaderCounts {
+  u32 parallel_bodies, parallel_units, no_index, unusable, mismatch, overflow;
+};
+void inflate_units_header_counts(const void* header, InflateUnitsHeaderCounts* c);
+
 // ---- deflate compress (deflate.hip; include/flare_deflate_compress_gpu.h).  The
 // call gets no input size: deflate_unit_capacity gives the units a workspace
 // holds (0: below deflate_workspace_bytes(n_msgs, 0)).
 size_t deflate_workspace_bytes(u32 n_msgs, u64 total_in_bytes);
 u64 deflate_unit_capacity(u32 n_msgs, size_t ws_bytes);
 hipError_t launch_deflate(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out, const u64* out_off,
-                          u32* out_len, i32* status, u32 format, u32 level, void* ws, size_t ws_bytes,
-                          hipStream_t stream);  // level: defl::kLevelStored / Fast / Best (deflate_format.h)
+                          u32* out_len, i32* status, u32 format, u32 level, u32 flags, void* ws, size_t ws_bytes,
+                          hipStream_t stream);  // level: defl::kLevelStored / Fast / Best (deflate_format.h);
+                                                // flags: gzidx::kFlagUnitIndex (gzip_index.h), gzip only
 struct DeflateHeaderCounts {
   u32 units, stored, fixed, dynamic, overflow;
 };

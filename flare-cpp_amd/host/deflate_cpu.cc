@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../csrc/deflate_format.h"
+#include "../csrc/gzip_index.h"
 #include "inflate_cpu.h"
 
 namespace {
@@ -154,19 +155,39 @@ int fsh_cpu_deflate(uint32_t format, const void* in, size_t n, void* out, size_t
   return fsh_cpu_deflate_level(format, kLevelFast, in, n, out, cap, len);
 }
 
-int fsh_cpu_deflate_level(uint32_t format, uint32_t level, const void* in_, size_t n, void* out_, size_t cap,
+int fsh_cpu_deflate_level(uint32_t format, uint32_t level, const void* in, size_t n, void* out, size_t cap,
                           uint64_t* len) {
+  return fsh_cpu_deflate_flags(format, level, 0, in, n, out, cap, len);
+}
+
+size_t fsh_cpu_deflate_bound_flags(size_t n, uint32_t format, uint32_t flags) {
+  if (format > kGzip || (flags & ~gzidx::kFlagUnitIndex) || (flags && format != kGzip)) return 0;
+  const uint64_t units = unit_count(n);
+  return (size_t)(max_length(n, format) +
+                  (gzidx::writes_index(format, flags, units) ? gzidx::head_bytes((uint32_t)units) - 10 : 0));
+}
+
+int fsh_cpu_deflate_flags(uint32_t format, uint32_t level, uint32_t flags, const void* in_, size_t n, void* out_,
+                          size_t cap, uint64_t* len) {
   *len = 0;
   if (format > kGzip || level > kMaxLevel) return infl::kStCorrupt;
+  if ((flags & ~gzidx::kFlagUnitIndex) || (flags && format != kGzip)) return infl::kStCorrupt;
   const uint8_t* in = static_cast<const uint8_t*>(in_);
-  std::vector<uint8_t> body(wrapper_head(format));
-  write_wrapper_head(format, body.data());
-  std::vector<Scratch> scratch(1);
   const uint64_t units = unit_count(n);
+  const bool index = gzidx::writes_index(format, flags, units);
+  const uint32_t head = index ? gzidx::head_bytes((uint32_t)units) : wrapper_head(format);
+  std::vector<uint8_t> body(head);
+  if (index)
+    gzidx::write_head((uint32_t)units, kUnit, body.data());
+  else
+    write_wrapper_head(format, body.data());
+  std::vector<Scratch> scratch(1);
   for (uint64_t u = 0; u < units; ++u) {
     const uint64_t first = u * kUnit;
     const uint32_t un = (uint32_t)(n - first < kUnit ? n - first : kUnit);
+    const size_t before = body.size();
     compress_unit(level, in + first, un, u + 1 == units, scratch[0], &body);
+    if (index) gzidx::wr16(body.data() + 22 + 2 * u, (uint32_t)(body.size() - before));  // at most 65,477
   }
   uint8_t tail[8];
   const uint32_t sum = format == kZlib ? fsh_cpu_adler32(in, n) : format == kGzip ? fsh_cpu_crc32(in, n) : 0u;

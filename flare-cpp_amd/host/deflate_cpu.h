@@ -32,6 +32,18 @@ int fsh_cpu_deflate(uint32_t format, const void *in, size_t n, void *out, size_t
 int fsh_cpu_deflate_level(uint32_t format, uint32_t level, const void *in, size_t n, void *out, size_t cap,
                           uint64_t *len);
 
+/* With flags (include/flare_deflate_index_gpu.h): the DEFINITION of the bytes
+ * fsg_deflate_batch_flags produces.  flags = 1 (FSG_DEFLATE_FLAG_UNIT_INDEX),
+ * gzip only: the 10-byte head is replaced by the 22 + 2 * units bytes of
+ * csrc/gzip_index.h (the units' compressed lengths in an `RA` extra
+ * subfield); the deflate stream and the trailer are those of flags = 0.  A
+ * body of more than 32,762 units is written without the index.  An unknown
+ * flag, or the flag with another format, is 1 (FSG_CORRUPT) with *len = 0.
+ * fsh_cpu_deflate_bound_flags: the slot bound (0 for what the call refuses). */
+size_t fsh_cpu_deflate_bound_flags(size_t n, uint32_t format, uint32_t flags);
+int fsh_cpu_deflate_flags(uint32_t format, uint32_t level, uint32_t flags, const void *in, size_t n, void *out,
+                          size_t cap, uint64_t *len);
+
 /* The block types of the units the last-named call would choose, for tests
  * and reports: counts[0..3) += stored, fixed, dynamic units of in[0 .. n). */
 void fsh_cpu_deflate_unit_types(const void *in, size_t n, uint64_t counts[3]);

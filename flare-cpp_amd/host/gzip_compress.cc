@@ -14,13 +14,13 @@ namespace {
 
 constexpr uint32_t kZlibFormat = 1, kGzipFormat = 2;  // FSG_INFLATE_ZLIB, FSG_INFLATE_GZIP
 
-bool Deflate(uint32_t format, const cord_buf& in, cord_buf* out, uint32_t level = 1) {
+bool Deflate(uint32_t format, const cord_buf& in, cord_buf* out, uint32_t level = 1, uint32_t flags = 0) {
   const size_t n = in.size();
   std::vector<uint8_t> src(n);
   in.copy_to(src.data(), n);
-  std::vector<uint8_t> body(fsh_cpu_deflate_bound(n, format));
+  std::vector<uint8_t> body(fsh_cpu_deflate_bound_flags(n, format, flags));
   uint64_t len = 0;
-  if (fsh_cpu_deflate_level(format, level, src.data(), n, body.data(), body.size(), &len) != 0) return false;
+  if (fsh_cpu_deflate_flags(format, level, flags, src.data(), n, body.data(), body.size(), &len) != 0) return false;
   return out->append(body.data(), len) == 0;
 }
 
@@ -69,7 +69,8 @@ bool GzipCompress(const cord_buf& in, cord_buf* out, const GzipCompressOptions* 
     format = kZlibFormat;
   else
     return false;
-  return Deflate(format, in, out, level);
+  if (options->unit_index && format != kGzipFormat) return false;  // zlib has no field to carry it
+  return Deflate(format, in, out, level, options->unit_index ? 1u : 0u);  // FSG_DEFLATE_FLAG_UNIT_INDEX
 }
 bool GzipDecompress(const cord_buf& in, cord_buf* out) { return Inflate(kGzipFormat, in, out); }
 bool ZlibCompress(const cord_buf& in, cord_buf* out) { return Deflate(kZlibFormat, in, out); }

@@ -8,7 +8,11 @@
 // of csrc/deflate_format.h: 0 -> 0 (stored units only), 1 .. 3 (zlib's greedy
 // levels) -> 1, 4 .. 9 and -1 (its lazy levels and its default) -> 2, anything
 // else returns false.  nullptr equals the two-argument function; the two-
-// argument functions write level 1.
+// argument functions write level 1.  unit_index (not the reference's; off by
+// default) writes a GZIP body with its units' compressed lengths in the
+// header's extra field (include/flare_deflate_index_gpu.h), which
+// fsg_inflate_units_batch decodes a wave per unit and every other inflate
+// skips; with ZLIB, which has no such field, it returns false.
 //
 // Compress writes the bodies csrc/deflate_format.h defines (host/deflate_cpu.h:
 // legal gzip / zlib streams that any inflate reads, not zlib's bytes);
@@ -28,6 +32,7 @@ struct GzipCompressOptions {
   enum Format { GZIP = 1, ZLIB = 2 };
   Format format = GZIP;
   int compression_level = -1;
+  bool unit_index = false;
 };
 bool GzipCompress(const cord_buf& in, cord_buf* out, const GzipCompressOptions* options);
 

@@ -59,18 +59,24 @@ inline uint32_t lookup(Reader& r, const uint32_t* tab, uint32_t root) {
   return e;
 }
 
-int inflate_body(uint32_t format, const uint8_t* p, uint64_t n, uint8_t* out, uint64_t cap, bool store,
-                 uint64_t* len_out) {
-  *len_out = 0;
-  if (format > kGzip || n > 0xffff0000ull) return kStCorrupt;  // the device decoder's limit (4 GiB - 64 KiB)
-  const Wrapper w = parse_wrapper(format, p, n);
-  if (w.status != kStOk) return w.status;
-  if (n < (uint64_t)w.begin + w.trailer) return kStCorrupt;
-  const uint64_t n_end = n - w.trailer;  // where the deflate stream must end
-  Reader r(p, n, w.begin);
+// The block loop over p[at ..): blocks until BFINAL, which must end in byte
+// n_end - 1 (a whole stream, or the last unit of an indexed gzip body).  With
+// `nonlast` it is a unit before the last (csrc/gzip_index.h): it ends clean
+// after the block whose last bit is bit 8 * n_end - 1, having given exactly
+// chlen bytes and met no BFINAL; everything else is kStCorrupt.  Distances are
+// counted from the walk's first output byte, out[0]; cap is the room at out.
+int walk(const uint8_t* p, uint64_t n, uint64_t at, uint64_t n_end, bool nonlast, uint64_t chlen, uint8_t* out,
+         uint64_t cap, bool store, uint64_t* outpos_out) {
+  Reader r(p, n, at);
   Tables t;
   uint64_t outpos = 0;
-  uint32_t last;
+  uint32_t last = 0;
+  auto unit_end = [&]() -> int {  // a non-last unit after each block; -1: go on
+    *outpos_out = outpos;
+    if (last || outpos > chlen) return kStCorrupt;
+    if (r.consumed() == 8 * n_end) return outpos == chlen ? kStOk : kStCorrupt;
+    return -1;
+  };
   do {
     r.need();
     last = r.bits(1);
@@ -86,6 +92,10 @@ int inflate_body(uint32_t format, const uint8_t* p, uint64_t n, uint8_t* out, ui
       for (uint32_t i = 0; i < len; ++i, ++outpos)
         if (store && outpos < cap) out[outpos] = p[start + i];
       r.restart(start + len);
+      if (nonlast) {
+        const int v = unit_end();
+        if (v >= 0) return v;
+      }
       continue;
     }
     const uint32_t *lt, *dt;
@@ -135,9 +145,27 @@ int inflate_body(uint32_t format, const uint8_t* p, uint64_t n, uint8_t* out, ui
       for (uint32_t i = 0; i < length; ++i, ++outpos)
         if (store && outpos < cap) out[outpos] = out[outpos - distance];
     }
+    if (nonlast) {
+      const int v = unit_end();
+      if (v >= 0) return v;
+    }
   } while (!last);
+  *outpos_out = outpos;
   const uint64_t used = r.consumed();
   if (used > 8 * n_end || (used + 7) / 8 != n_end) return kStCorrupt;  // cut short, or bytes after the stream
+  return kStOk;
+}
+
+int inflate_body(uint32_t format, const uint8_t* p, uint64_t n, uint8_t* out, uint64_t cap, bool store,
+                 uint64_t* len_out) {
+  *len_out = 0;
+  if (format > kGzip || n > 0xffff0000ull) return kStCorrupt;  // the device decoder's limit (4 GiB - 64 KiB)
+  const Wrapper w = parse_wrapper(format, p, n);
+  if (w.status != kStOk) return w.status;
+  if (n < (uint64_t)w.begin + w.trailer) return kStCorrupt;
+  const uint64_t n_end = n - w.trailer;  // where the deflate stream must end
+  uint64_t outpos = 0;
+  if (walk(p, n, w.begin, n_end, false, 0, out, cap, store, &outpos) != kStOk) return kStCorrupt;
   if (!store) {
     *len_out = outpos;
     return kStOk;
@@ -174,6 +202,15 @@ int fsh_cpu_inflate(uint32_t format, const void* in, size_t n, void* out, size_t
 int fsh_cpu_inflate_length(uint32_t format, const void* in, size_t n, uint64_t* len) {
   uint64_t l = 0;
   const int st = inflate_body(format, static_cast<const uint8_t*>(in), n, nullptr, 0, false, &l);
+  if (len) *len = l;
+  return st;
+}
+
+int fsh_cpu_inflate_unit(const void* in, size_t n, size_t start, size_t stop, int nonlast, uint32_t chlen, void* out,
+                         size_t cap, int store, uint64_t* len) {
+  uint64_t l = 0;
+  const int st = walk(static_cast<const uint8_t*>(in), n, start, stop, nonlast != 0, chlen, static_cast<uint8_t*>(out),
+                      cap, store != 0, &l);
   if (len) *len = l;
   return st;
 }

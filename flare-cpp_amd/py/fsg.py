@@ -18,7 +18,8 @@ LIB_DIR = PKG_DIR / "lib"
 REPO_DIR = PKG_DIR.parent
 HEADER = REPO_DIR / "include" / "flare_snappy_gpu.h"
 HEADERS = (HEADER, REPO_DIR / "include" / "flare_lz4_gpu.h", REPO_DIR / "include" / "flare_deflate_gpu.h",
-           REPO_DIR / "include" / "flare_deflate_compress_gpu.h", REPO_DIR / "include" / "flare_deflate_level_gpu.h")
+           REPO_DIR / "include" / "flare_deflate_compress_gpu.h", REPO_DIR / "include" / "flare_deflate_level_gpu.h",
+           REPO_DIR / "include" / "flare_deflate_index_gpu.h")
 
 FSG_OK, FSG_CORRUPT, FSG_BAD_HEADER, FSG_SLOT_TOO_SMALL, FSG_IOV_TOO_SMALL = 0, 1, 2, 3, 4
 FSG_FLAG_VALIDATE_ONLY, FSG_FLAG_STRICT_HEADER = 1, 2
@@ -59,6 +60,11 @@ DeflateReport = _report_struct("DeflateReport", (
 INFLATE_RAW, INFLATE_ZLIB, INFLATE_GZIP = 0, 1, 2
 # fsg_deflate_batch_level's levels (FSG_DEFLATE_LEVEL_*, include/flare_deflate_level_gpu.h)
 DEFLATE_LEVEL_STORED, DEFLATE_LEVEL_FAST, DEFLATE_LEVEL_BEST = 0, 1, 2
+# fsg_deflate_batch_flags' flag and struct fsg_inflate_units_report (include/flare_deflate_index_gpu.h)
+DEFLATE_FLAG_UNIT_INDEX = 1
+InflateUnitsReport = _report_struct("InflateUnitsReport", (
+    "parallel_messages", "parallel_units", "serial_no_index", "serial_unusable_index", "serial_unit_mismatch",
+    "serial_workspace", "unit_entries"))
 PATH_MAIN, PATH_SINGLE_DESIGN, PATH_NO_WORKSPACE, PATH_FORCED = 0, 1, 2, 3
 
 _SIGS = {
@@ -120,6 +126,12 @@ _SIGS = {
     "fsg_deflate_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp]),
     "fsg_deflate_report": (_c.c_int, [_vp, _u32, _sz, _c.POINTER(DeflateReport)]),
     "fsg_deflate_batch_level": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _sz, _vp]),
+    "fsg_deflate_max_length_flags": (_sz, [_sz, _u32, _u32]),
+    "fsg_deflate_batch_flags": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _sz, _vp]),
+    "fsg_inflate_units_workspace_bytes": (_sz, [_u32, _u64]),
+    "fsg_inflate_units_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _sz, _vp]),
+    "fsg_inflate_units_lengths_batch": (_c.c_int, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _sz, _vp]),
+    "fsg_inflate_units_report": (_c.c_int, [_vp, _u32, _sz, _c.POINTER(InflateUnitsReport)]),
 }
 
 
@@ -142,7 +154,9 @@ _OPTIONAL = {"fsg_decompress_batch_2s", "fsg_decompress_batch_partial", "fsg_dec
              "fsg_lz4f_max_frame_length_flags", "fsg_lz4f_xxh32_batch", "fsg_lz4f_compress_batch_flags",
              "fsg_inflate_batch", "fsg_inflate_lengths_batch", "fsg_crc32_batch", "fsg_adler32_batch",
              "fsg_deflate_max_length", "fsg_deflate_workspace_bytes", "fsg_deflate_batch", "fsg_deflate_report",
-             "fsg_deflate_batch_level"}
+             "fsg_deflate_batch_level", "fsg_deflate_max_length_flags", "fsg_deflate_batch_flags",
+             "fsg_inflate_units_workspace_bytes", "fsg_inflate_units_batch", "fsg_inflate_units_lengths_batch",
+             "fsg_inflate_units_report"}
 
 
 def load_gpu_lib(path: Path | None = None) -> ctypes.CDLL:
@@ -451,6 +465,52 @@ class SnappyGPU:
         head, nbytes = self._report_header(workspace)
         r = DeflateReport()
         self._check(self.lib.fsg_deflate_report(head, n, nbytes, _c.byref(r)), "fsg_deflate_report")
+        return self._report_dict(r)
+
+    # ---- the unit index (include/flare_deflate_index_gpu.h)
+    def deflate_max_length_flags(self, n, fmt=INFLATE_GZIP, flags=DEFLATE_FLAG_UNIT_INDEX) -> int:
+        return self.lib.fsg_deflate_max_length_flags(n, fmt, flags)
+
+    def deflate_flags(self, d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_len, d_status, workspace,
+                      fmt=INFLATE_GZIP, level=DEFLATE_LEVEL_FAST, flags=DEFLATE_FLAG_UNIT_INDEX, stream=None):
+        """fsg_deflate_batch_flags: fsg_deflate_batch_level with a flags word
+        (DEFLATE_FLAG_UNIT_INDEX: gzip bodies that carry their units'
+        compressed lengths) into slots of deflate_max_length_flags bytes."""
+        ws = 0 if workspace is None else workspace.numel() * workspace.element_size()
+        self._check(self.lib.fsg_deflate_batch_flags(
+            _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len),
+            _ptr(d_status), fmt, level, flags, _ptr(workspace), ws, self._stream(stream)), "fsg_deflate_batch_flags")
+
+    def inflate_units_workspace_bytes(self, n, extra_units) -> int:
+        return self.lib.fsg_inflate_units_workspace_bytes(n, extra_units)
+
+    def inflate_units_workspace(self, n, extra_units, device=None):
+        import torch
+        nbytes = self.inflate_units_workspace_bytes(n, extra_units)
+        return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device or f"cuda:{self.device}")
+
+    def inflate_units(self, d_in, d_in_off, d_in_len, n, d_out, d_out_off, d_out_cap, d_out_len, d_status,
+                      workspace, fmt=INFLATE_GZIP, stream=None):
+        """fsg_inflate_units_batch: fsg_inflate_batch's results, a wave per
+        unit for the gzip bodies that carry a usable unit index."""
+        ws = 0 if workspace is None else workspace.numel() * workspace.element_size()
+        self._check(self.lib.fsg_inflate_units_batch(
+            _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_out), _ptr(d_out_off), _ptr(d_out_cap),
+            _ptr(d_out_len), _ptr(d_status), fmt, _ptr(workspace), ws, self._stream(stream)),
+            "fsg_inflate_units_batch")
+
+    def inflate_units_lengths(self, d_in, d_in_off, d_in_len, n, d_length, d_status, workspace, fmt=INFLATE_GZIP,
+                              stream=None):
+        """fsg_inflate_units_lengths_batch: fsg_inflate_lengths_batch's results by units."""
+        ws = 0 if workspace is None else workspace.numel() * workspace.element_size()
+        self._check(self.lib.fsg_inflate_units_lengths_batch(
+            _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), n, _ptr(d_length), _ptr(d_status), fmt, _ptr(workspace), ws,
+            self._stream(stream)), "fsg_inflate_units_lengths_batch")
+
+    def inflate_units_report(self, workspace, n) -> dict:
+        head, nbytes = self._report_header(workspace)
+        r = InflateUnitsReport()
+        self._check(self.lib.fsg_inflate_units_report(head, n, nbytes, _c.byref(r)), "fsg_inflate_units_report")
         return self._report_dict(r)
 
     # ---- path reports (fsg_decompress_report and its kin)
