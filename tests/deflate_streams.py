@@ -2,8 +2,13 @@
 with it.  The writer takes chosen code lengths and a token list and returns the
 bits, so a test can place what zlib's compressor never emits: 15-bit codes, a
 single distance code, symbols without a code, broken headers.  Nothing here
-decodes; Python's zlib (1.2.11, the library the reference calls) is the judge
-(`zlib_verdict`).
+decodes; Python's zlib (the library the reference calls) is the judge
+(`zlib_verdict`).  zlib.ZLIB_RUNTIME_VERSION read 1.2.11 both on the host where
+the CPU tests were written and on the MI355X host where the GPU tests ran, so
+no stream was judged by two releases; the acceptance rules for deflate streams
+have not changed between zlib releases, only the compressor's bytes may (the
+digests of test_writer_changes_keep_the_old_vectors hold for 1.2.11's).
+tests/deflate_random.py builds the seeded random family with this writer.
 
 Tokens of a block: an int 0..255 is a literal; (length, distance) is a copy;
 ("ll", sym) is a raw literal/length symbol with no extra bits (286, 287);
@@ -91,8 +96,8 @@ class Bits:
 
     def code(self, code, nbits):
         """A Huffman code: most significant bit first."""
-        for i in range(nbits - 1, -1, -1):
-            self.put((code >> i) & 1, 1)
+        if nbits:  # the low nbits of the code (an over-subscribed set's codes can be wider), reversed
+            self.put(int(format(code & ((1 << nbits) - 1), f"0{nbits}b")[::-1], 2), nbits)
 
     def align(self):
         if self.n:
@@ -110,6 +115,7 @@ class Bits:
 class Deflate:
     def __init__(self):
         self.b = Bits()
+        self.headers = []  # (first bit, end bit) of every dynamic block header written, BFINAL to the last length
 
     def header(self, final, btype):
         self.b.put(1 if final else 0, 1)
@@ -123,8 +129,11 @@ class Deflate:
         self.b.out += data
         return self
 
-    def tokens(self, toks, ll, dd, eob=True):
+    def tokens(self, toks, ll, dd, eob=True, marks=None):
+        """marks: a list that receives the bit position at which each token starts."""
         for t in toks:
+            if marks is not None:
+                marks.append(self.b.bitpos)
             if isinstance(t, int):
                 self.b.code(*ll[t])
             elif t[0] == "ll":
@@ -150,20 +159,23 @@ class Deflate:
         return self
 
     def dynamic(self, ll_lens, d_lens, toks, final=False, eob=True, cl_lens=None, cl_syms=None, hlit=None,
-                hdist=None, body=True):
+                hdist=None, body=True, hclen=19, marks=None):
         """ll_lens / d_lens: the code lengths the header declares.  cl_lens:
         the 19 code-length code lengths (default: a complete code over all 19);
         cl_syms: the code-length symbols to send as (sym, extra value) pairs
         (default: one plain length per symbol, no repeats).  hlit / hdist
-        override the header's counts.  body=False: the header alone."""
+        override the header's counts.  body=False: the header alone.  hclen: how
+        many code-length code lengths are sent (4..19, in CL_ORDER); the rest are
+        implied zero.  marks: see tokens()."""
+        start = self.b.bitpos
         self.header(final, 2)
         ll_lens, d_lens = list(ll_lens), list(d_lens)
         if cl_lens is None:
             cl_lens = [4] * 13 + [5] * 6
         self.b.put((len(ll_lens) - 257) if hlit is None else hlit, 5)
         self.b.put((len(d_lens) - 1) if hdist is None else hdist, 5)
-        self.b.put(19 - 4, 4)
-        for s in CL_ORDER:
+        self.b.put(hclen - 4, 4)
+        for s in CL_ORDER[:hclen]:
             self.b.put(cl_lens[s], 3)
         cl = canonical(cl_lens)
         if cl_syms is None:
@@ -172,8 +184,9 @@ class Deflate:
             self.b.code(*cl[sym])
             if sym >= 16:
                 self.b.put(extra, {16: 2, 17: 3, 18: 7}[sym])
+        self.headers.append((start, self.b.bitpos))
         if body:
-            self.tokens(toks, canonical(ll_lens), canonical(d_lens), eob)
+            self.tokens(toks, canonical(ll_lens), canonical(d_lens), eob, marks)
         return self
 
     def raw(self) -> bytes:

@@ -4,8 +4,11 @@ shares) against Python's zlib -- bodies zlib's compressor writes, hand-built
 streams from tests/deflate_streams.py, one rejected stream per cause with the
 exact status and zlib's refusal beside it, 2,000 single-bit flips per format
 -- then the same vectors under AddressSanitizer and UBSan in a stand-alone
-program, and the new header's symbols and argument checks."""
+program, and the new header's symbols and argument checks.  The seeded family
+of tests/deflate_random.py (random hand-built streams and the worst-case code
+tables) runs through the same checks, with floors on what it covers."""
 import ctypes
+import hashlib
 import shutil
 import struct
 import subprocess
@@ -14,6 +17,7 @@ from pathlib import Path
 
 import pytest
 
+import deflate_random as R
 import deflate_streams as D
 import fsg
 
@@ -155,6 +159,14 @@ def check_vectors():
         for body, want in D.mutation_set(fmt)[:300]:
             if want is not None:
                 rec.append((fmt, body, len(want), D.OK, want))
+    fam = R.random_family()
+    for k, s in enumerate(fam[:8] + fam[8::10]):  # the worst-case tables and every tenth random stream
+        fmt = k % 3
+        n = len(s.expected)
+        rec.append((fmt, s.body(fmt), n, D.OK, s.expected))
+        cap = R.inner_capacity(s, fmt)[0]
+        if cap is not None:
+            rec.append((fmt, s.body(fmt), cap, D.SLOT_TOO_SMALL, s.expected))
     return rec
 
 
@@ -177,6 +189,120 @@ def test_host_model_sanitized(tmp_path):
     r = subprocess.run([str(exe), str(tmp_path / "vectors.bin")], capture_output=True, text=True, timeout=600,
                        env={"ASAN_OPTIONS": "detect_leaks=0"})
     assert r.returncode == 0 and r.stdout.strip() == f"ok {len(rec)}", r.stdout[-2000:] + r.stderr[-3000:]
+
+
+# ---- the seeded family of tests/deflate_random.py
+
+def vector_digest(vectors):
+    h = hashlib.sha256()
+    for v in vectors:
+        for x in v:
+            x = x if isinstance(x, bytes) else str(x).encode()
+            h.update(len(x).to_bytes(4, "little") + x)
+    return h.hexdigest()
+
+
+def test_writer_changes_keep_the_old_vectors():
+    """The digests were taken before Deflate.dynamic got hclen and Bits.code
+    stopped putting bit by bit.  The hand-built streams depend on the writer
+    alone; the whole sets also hold zlib 1.2.11's compressor output."""
+    assert vector_digest(D.accept_streams()) == "813e0aa3c80aa4a5ff9d1309823bb15385341149fc2082a421a09ab15cf2bc08"
+    assert vector_digest(D.accept_vectors()) == "4fe8f586d18e5f8b26a431ec65eaeaafd6a34ae0450e7d0faab87b0d2484a0f6"
+    assert vector_digest(D.reject_streams()) == "75219d17b9ff4a37893b34185dc302a6258055bf819c759ffc63ded5a50e36c0"
+
+
+FORMATS = [D.RAW, D.ZLIB, D.GZIP]
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_random_family_is_valid_for_zlib(fmt):
+    """A generator bug fails here, not on the GPU."""
+    for s in R.random_family():
+        got = D.zlib_verdict(fmt, s.body(fmt))
+        assert got is not None, s.name
+        assert got == s.expected, s.name
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_random_family_host_model(host, fmt):
+    for s in R.random_family():
+        body, n = s.body(fmt), len(s.expected)
+        assert inflate(host, fmt, body, n) == (D.OK, n, s.expected), s.name
+        assert length(host, fmt, body) == (D.OK, n), s.name
+        for cap in sorted({0, n - 1, R.inner_capacity(s, fmt)[0]} - {None, -1, n}):
+            assert inflate(host, fmt, body, cap) == (D.SLOT_TOO_SMALL, n, None), (s.name, cap)
+
+
+def test_random_family_coverage():
+    """Floors on what the generator places; table_entries restates the
+    decoder's sizing rule and only measures the family."""
+    fam = R.random_family()
+    assert len(fam) == 308 and sum(len(s.raw) for s in fam) < 1_500_000
+    assert R.table_entries([0] * 30, 6) == 2 and R.table_entries([0, 1], 6) == 2
+    assert R.table_entries(D.FIXED_LL, 9) == 512 and R.table_entries(D.FIXED_D, 6) == 32
+    staircase = list(range(1, 15)) + [15, 15]  # dynamic_15_bit_codes: 512 + 64
+    assert R.table_entries(staircase, 9) == 576
+    for s in fam[:8]:
+        ll, dd = s.stats["ll_lens"], s.stats["d_lens"]
+        assert R.table_entries(ll, 9) == 852 and R.table_entries(dd, 6) == 592, s.name
+        assert all(ll) and all(dd) and len(ll) == 286 and len(dd) == 30  # every symbol is coded and used
+        assert s.stats["used_ll"] == set(range(286)) and s.stats["used_d"] == set(range(30)), s.name
+    for s in fam[:2]:  # the 48-bit symbol (15 + 5 + 15 + 13 bits) at the phases of the 32-bit refill
+        ll, dd = s.stats["ll_lens"], s.stats["d_lens"]
+        assert sorted(i for i, n in enumerate(ll) if n == 15)[0] >= 281 and ll[285] != 15
+        assert dd[28] == dd[29] == 15
+        marks = s.stats["long_marks"]
+        assert s.stats["longest_run"] >= 40 and len({m % 32 for m in marks}) >= 16
+    total, hclens = R.family_totals()
+    assert total["ll_15_bit"] >= 50 and total["d_15_bit"] >= 50
+    for kind in ("stored", "fixed", "dynamic"):
+        assert total[kind] >= 200, kind
+    assert total["stored_len_0"] >= 1 and total["stored_len_65535"] >= 1 and total["stored_misaligned"] >= 100
+    assert total["no_distance_code"] >= 5 and total["single_distance_code"] >= 5
+    assert total["boundary_repeat_headers"] >= 30
+    assert len(hclens) >= 8
+    assert total["cl_7_bit"] >= 20
+    for cls in R.DIST_CLASSES:
+        assert total["d_" + cls] >= 500, cls
+    assert total["groups64_over_12000"] >= 20
+    assert total["groups64_all_258"] >= 1
+    assert total["chains_over_24"] >= 20 and total["max_chain"] >= 36  # resolution through dozens of records
+    for fmt in FORMATS:  # what the device's count-only test relies on
+        inside = [R.inner_capacity(s, fmt)[1] for s in fam]
+        assert inside.count("copy") >= 100 and inside.count("stored") >= 20, fmt
+
+
+def test_hand_built_unit_bodies(host):
+    """The indexed gzip bodies of the device's units test: zlib's bytes are
+    the generator's, the unit slices inflate alone where no unit reaches below
+    its first byte, and the host model's route says so."""
+    import gzip_index_cases as G
+    cases = R.unit_bodies()
+    assert len(cases) == 40 and sum(not p for _, _, p in cases) == 5
+    for body, data, parallel in cases:
+        assert D.zlib_verdict(D.GZIP, body) == data
+        assert inflate(host, D.GZIP, body, len(data)) == (D.OK, len(data), data)
+        route, units = G.route(body, len(data))
+        assert 2 <= units <= 6
+        if parallel:
+            assert route == G.PARALLEL and G.slices(body) == data
+        else:
+            assert route == G.MISMATCH and G.slices(body) is None
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_hand_built_flips_match_zlib(host, fmt):
+    accepted = 0
+    flips = R.hand_flip_set(fmt)
+    for body, want in flips:
+        cap = len(want) if want is not None else 8192
+        st, ln, got = inflate(host, fmt, body, cap)
+        assert (st == D.OK) == (want is not None), (fmt, body.hex())
+        if want is not None:
+            assert got == want
+            accepted += 1
+    if fmt == D.RAW:  # neither side of the comparison is empty
+        assert 0.05 * len(flips) <= accepted <= 0.95 * len(flips), accepted
 
 
 # ---- the public header and the argument checks, no GPU

@@ -6,11 +6,13 @@ exactly what fsg_inflate_batch gives -- the index changes the route, never the
 result -- and the route each body took (fsg_inflate_units_report) is the one
 the host model (fsh_cpu_inflate_units_route) names.  Python's zlib judges the
 bytes.  Bodies: tests/gzip_index_cases.py (this project's flagged bodies and
-foreign ones written by zlib with a full flush per chunk).  Every call runs
-under the containment guards of tests/inflate_units_harness.py."""
+foreign ones written by zlib with a full flush per chunk) and the hand-built
+units of tests/deflate_random.py.  Every call runs under the containment
+guards of tests/inflate_units_harness.py."""
 import numpy as np
 import pytest
 
+import deflate_random as R
 import deflate_streams as D
 import gzip_index_cases as G
 
@@ -125,6 +127,22 @@ def test_bit_flips_over_an_indexed_body(gpu):
     assert in_index >= 3
     assert rep["parallel_messages"] > 0 and rep["serial_unit_mismatch"] > 0 and rep["serial_unusable_index"] > 0
     assert rep["serial_workspace"] == 0
+
+
+def test_hand_built_units(gpu):
+    """40 bodies of 2 to 6 units made of random blocks of every type, each
+    unit in front of the last closed by an empty stored block: one wave per
+    unit.  In 5 of them a unit copies from below its first byte, so the body
+    is walked as one stream.  Either way the bytes are zlib's."""
+    cases = R.unit_bodies()
+    bodies = [b for b, _, _ in cases]
+    wants = [D.zlib_verdict(D.GZIP, b) for b in bodies]
+    for (_, data, parallel), body, want in zip(cases, bodies, wants):
+        assert want == data
+        assert G.route(body, len(data))[0] == (G.PARALLEL if parallel else G.MISMATCH)
+    rep = check_parity(gpu, bodies, [len(w) for w in wants], D.GZIP, layout="tight", wants=wants)
+    assert rep["parallel_messages"] == 35 and rep["serial_unit_mismatch"] == 5
+    assert rep["parallel_units"] == sum(G.route(b)[1] for b, _, p in cases if p)
 
 
 def test_capacities(gpu):
