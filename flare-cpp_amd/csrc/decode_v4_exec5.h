@@ -35,6 +35,7 @@ namespace fsg {
 // ===========================================================================
 namespace {
 constexpr u32 kGroupBytes = 1024;  // output bytes per group (as v4: 64 pieces x 16)
+static_assert(kExecRing == kTagRing, "decode_v4_plan.h sizes the folded instance's window from the ring");
 
 // Per tag byte c: bits 0-4 the right shift of 0xffffffff that masks the nb
 // extra bytes ((32 - 8 nb) & 31), bit 5 long literal (length = extra + 1),
@@ -60,15 +61,32 @@ __device__ __forceinline__ u32 exec_tag_entry(u32 c) {
 }
 }  // namespace
 
+// Two instances (exec_kernel<5>):
+//   - folded, <true, u16, kWindowWhole>: a whole body of at most big_threshold
+//     compressed bytes (every wave-per-message block).  The range it decodes
+//     is the whole message, so ip0 = 0, op0 = 0 and op1 = out_len[m] are
+//     constants (the arguments are ignored) and the range tests fold away; a
+//     tag position is below kBigIndexMax < 2^16, so the ring holds 16-bit
+//     entries, and the KiB that frees goes to the window;
+//   - general, <false, u32, kWindow>: the listed large messages, whole or one
+//     64 KiB segment [op0, op1) of the output starting at input offset ip0.
+// Per wave both use 4 kTagRing + kWindow + 32 bytes of LDS: the ring
+// (sizeof(RingT) kTagRing bytes), then the window (kWin + 32).
+template <bool kWhole, typename RingT, u32 kWin>
 __device__ __forceinline__ void exec5_message(
     u32 m, const u8* __restrict__ in, const u64* __restrict__ in_off,
     const u32* __restrict__ in_len, u8* out, const u64* __restrict__ out_off,
     const u32* __restrict__ out_len, i32* __restrict__ status, const u32* __restrict__ bm_base,
-    const u32* __restrict__ bitmap, u32* ring, const u32* tagtab, u8* sb, const u32x4* sel_tab,
-    const u32x4* mtab, u32 lane, i32 st, u32 ip0, u32 op0, u32 op1, bool prio, u32 keep_hist) {
+    const u32* __restrict__ bitmap, RingT* ring, const u32* tagtab, u8* sb, const u32x4* sel_tab,
+    const u32x4* mtab, u32 lane, i32 st, u32 ip0_, u32 op0_, u32 op1_, bool prio, u32 keep_hist) {
+  static_assert(sizeof(RingT) == 4 || (kWhole && sizeof(RingT) == 2 && kBigIndexMax < 65536),
+                "16-bit ring entries: tag positions of a body of at most big_threshold bytes");
+  static_assert(sizeof(RingT) * kTagRing + kWin == 4 * kTagRing + kWindow && kWin % 16 == 0,
+                "ring + window fill the wave's LDS");
   const u32 bmb = bm_base[m];
   const u32 n_in = in_len[m];
   const u32 expected = out_len[m];
+  const u32 ip0 = kWhole ? 0u : ip0_, op0 = kWhole ? 0u : op0_, op1 = kWhole ? expected : op1_;
   const u8* ib = in + in_off[m];
   u8* ob = out + out_off[m];
   if (st != kOk) return;
@@ -105,7 +123,7 @@ __device__ __forceinline__ void exec5_message(
   u32 flushed = op0;                                    // output [op0, flushed) is in global memory
   auto zero_from = [&](u32 from) {  // 1 KiB of zeros at a 16-aligned offset
     const u32 i = from + 16 * lane;
-    if (i < kWindow + 32) *reinterpret_cast<u32x4*>(sb + i) = u32x4{0, 0, 0, 0};
+    if (i < kWin + 32) *reinterpret_cast<u32x4*>(sb + i) = u32x4{0, 0, 0, 0};
   };
   zero_from(0);
   u32 zero_end = 1024;
@@ -153,7 +171,7 @@ __device__ __forceinline__ void exec5_message(
       const u32 incl = dpp_incl_scan(cnt);
       u32 slot = tail + incl - cnt;
       while (bits) {
-        ring[slot & (kTagRing - 1)] = bitbase + __builtin_ctz(bits);
+        ring[slot & (kTagRing - 1)] = (RingT)(bitbase + __builtin_ctz(bits));
         ++slot;
         bits &= bits - 1;
       }
@@ -256,7 +274,7 @@ __device__ __forceinline__ void exec5_message(
     }
 
     // ---------- slide the window if this group would overrun it (as v4)
-    if (op + tot_len - sbase > kWindow) {
+    if (op + tot_len - sbase > kWin) {
       const int nsb = (int)(((op - keep_hist + obal) & ~15u)) - (int)obal;
       if ((int)flushed < nsb + 16) flush_to((u32)((int)((op + obal) & ~15u) - (int)obal));
       wait_all_memory();

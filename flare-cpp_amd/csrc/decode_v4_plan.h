@@ -76,6 +76,28 @@ constexpr u32 kKeep = FSG_KEEP;      // history kept when the window slides
 // bytes.
 constexpr u32 kMaxKeep = (kWindow - 16 * 64 - 48) & ~15u;
 static_assert(kKeep <= kMaxKeep, "kept history leaves room for one group");
+// exec_kernel<5>'s folded instance (whole bodies of at most big_threshold
+// compressed bytes, one wave each; decode_v4_exec5.h): its tag positions fit
+// 16 bits (big_threshold <= kBigIndexMax), so its ring takes half the bytes of
+// the general instance's and its window the KiB that frees -- the same LDS
+// per wave.  Kept history (C3, A/B on one box, DESIGN.md section 5,
+// "Execution pass: folded instance"): 1,024 5.635 ms, 1,536 5.585, 2,048
+// 5.579, 3,024 (the largest) 5.636; the parent's 3 KiB window 5.759.
+constexpr u32 kExecRing = 512;  // tag positions per wave (= kTagRing, decode_v4_exec_common.h)
+static_assert(kBigIndexMax < 65536, "the folded instance's ring entries are 16 bits");
+constexpr u32 kWindowWhole = kWindow + 2 * kExecRing;
+#ifndef FSG_KEEP_WHOLE
+#define FSG_KEEP_WHOLE 2048
+#endif
+constexpr u32 kKeepWhole = FSG_KEEP_WHOLE;
+constexpr u32 kMaxKeepWhole = (kWindowWhole - 16 * 64 - 48) & ~15u;
+static_assert(kKeepWhole <= kMaxKeepWhole && kKeepWhole % 16 == 0, "kept history leaves room for one group");
+// LDS per wave of exec_kernel and exec_packed_kernel: ring, window and the 32
+// bytes an OR store may write past it -- either instance.
+constexpr u32 exec_wave_lds_bytes(bool whole) {
+  return (whole ? 2 * kExecRing + kWindowWhole : 4 * kExecRing + kWindow) + 32;
+}
+static_assert(exec_wave_lds_bytes(true) == exec_wave_lds_bytes(false), "one LDS carve-up per wave");
 // Path report: the packed pass counts the bodies it hands to pass 3 in the
 // workspace header, at these u32 slots after its batch counter (kWsPackNext).
 constexpr u32 kPackCtrWide = 3, kPackCtrGuard = 4;
@@ -211,7 +233,7 @@ struct DecodePlan {
   u32 big_threshold;  // compressed size above which a message takes pass 1b
   // ---- options, range-checked
   bool split_huge, walk_order, fork;
-  u32 split_mode, split_class, prio, keep_hist, pack_batch;
+  u32 split_mode, split_class, prio, keep_hist, keep_hist_whole, pack_batch;
   // ---- launches
   WalkKind walk_kind;      // the lane walk without a plan pass (one stream, two-stream form)
   LaunchDim walk;          //   its launch
@@ -326,11 +348,16 @@ inline DecodePlan decode_v4_plan(u32 n_msgs, size_t ws_bytes, bool two_stream, c
   p.prio = o.exec_prio != 0 ? 1u : 0u;  // A/B knob: 0 disables the priority raise
   // history kept when an exec window slides (option exec_keep: the tests
   // shrink it to exercise the slide's flush rule; 512..kMaxKeep bytes, a
-  // multiple of 16; anything else is the default)
+  // multiple of 16; anything else is the default).
+  // Per instance of exec_kernel<5>: keep_hist the general one (and variant 4,
+  // the packed pass), keep_hist_whole the folded one, whose wider window
+  // admits up to kMaxKeepWhole: a value above kMaxKeep sets it alone.
   p.keep_hist = kKeep;
+  p.keep_hist_whole = kKeepWhole;
   {
     const i64 v = o.exec_keep;
     if (v >= 512 && v <= (i64)kMaxKeep && v % 16 == 0) p.keep_hist = (u32)v;
+    if (v >= 512 && v <= (i64)kMaxKeepWhole && v % 16 == 0) p.keep_hist_whole = (u32)v;
   }
   const i64 fork_opt = o.decode_fork;
   p.fork = !two_stream && (fork_opt >= 0 ? fork_opt != 0 : n_msgs > 131072u);

@@ -63,6 +63,7 @@
 #include "wave_util.h"
 
 #include <mutex>
+#include <type_traits>
 
 #include "decode_v4_plan.h"
 #include "launch.h"
@@ -84,7 +85,9 @@ static_assert(kWave == 64, "idx_lean_lds_bytes (decode_v4_plan.h) counts 64 lane
 // block with the 3 KiB window: C3 6.35 -> 6.20 ms against 6 waves with a
 // 4 KiB window, A/B on one box; 8 waves spill and were slower).
 // The v4 variant (exec_kernel<4>) shares the setting and was not re-measured
-// at 7.
+// at 7.  Variant 5's folded instance (wave-per-message bodies) has a 4 KiB
+// window in the same LDS, its ring entries being 16 bits: C3 5.76 -> 5.58 ms,
+// DESIGN.md §5 "Execution pass: folded instance".
 // The first kBigBlocks blocks take the large messages listed by pass 1 from a
 // device counter (blocks dispatch in order, so the longest messages start
 // first); every other block runs the wave-per-message mapping and skips them.
@@ -115,24 +118,34 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) __attribute__((amdgpu_waves_pe
   if constexpr (V == 5) tagtab[threadIdx.x] = exec_tag_entry(threadIdx.x);
   init_mask_table(mask_tab, threadIdx.x);
   __syncthreads();
-  // one message (or segment) with the pass-2 variant V
-  auto run = [&](u32 m, u32* ring, u8* pmap, u8* sb, u32 lane, i32 st, u32 ip0, u32 op0, u32 op1) {
-    if constexpr (V == 5)
-      exec5_message(m, in, in_off, in_len, out, out_off, out_len, status, bm_base, bitmap, ring, tagtab,
-                    sb, sel_tab, mask_tab, lane, st, ip0, op0, op1, prio != 0, keep_hist);
-    else
-      exec_message(m, in, in_off, in_len, out, out_off, out_len, status, bm_base, bitmap, ring, pmap,
-                   sb, sel_tab, mask_tab, lane, st, ip0, op0, op1, prio != 0, keep_hist);
-  };
-
   // wave index made visibly uniform: the message's sizes, pointers and the
   // walk state (head, tail, op, window base) then live in SGPRs and branches
   // on them are scalar
   const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const u32 lane = threadIdx.x & 63;
-  u32* ring = reinterpret_cast<u32*>(wl_s[wv]);
+  u8* wl = wl_s[wv];
   u8* pmap = pmap_s[wv];
-  u8* sb = wl_s[wv] + 4 * kTagRing;
+  // One message (or segment) with the pass-2 variant V.  Variant 5 has two
+  // instances of exec5_message, one call site each: the folded one
+  // (whole = true_type: a whole body of at most big_threshold bytes; 16-bit
+  // ring, kWindowWhole window) and the general one.  keep_hist carries the
+  // kept history of both: the general instance's in bits 0-15, the folded
+  // one's in bits 16-31.
+  auto run = [&](auto whole, u32 m, i32 st, u32 ip0, u32 op0, u32 op1) {
+    constexpr bool kWhole = decltype(whole)::value;
+    if constexpr (V == 5 && kWhole)
+      exec5_message<true, u16, kWindowWhole>(m, in, in_off, in_len, out, out_off, out_len, status, bm_base, bitmap,
+                                             reinterpret_cast<u16*>(wl), tagtab, wl + 2 * kTagRing, sel_tab,
+                                             mask_tab, lane, st, 0u, 0u, 0u, prio != 0, keep_hist >> 16);
+    else if constexpr (V == 5)
+      exec5_message<false, u32, kWindow>(m, in, in_off, in_len, out, out_off, out_len, status, bm_base, bitmap,
+                                         reinterpret_cast<u32*>(wl), tagtab, wl + 4 * kTagRing, sel_tab, mask_tab,
+                                         lane, st, ip0, op0, op1, prio != 0, keep_hist & 0xffffu);
+    else
+      exec_message(m, in, in_off, in_len, out, out_off, out_len, status, bm_base, bitmap,
+                   reinterpret_cast<u32*>(wl), pmap, wl + 4 * kTagRing, sel_tab, mask_tab, lane, st, ip0, op0, op1,
+                   prio != 0, keep_hist & 0xffffu);
+  };
 
   if (blockIdx.x >= big_blocks) {
     // one message per wave; or, with small_stride (blocks), every
@@ -141,24 +154,25 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) __attribute__((amdgpu_waves_pe
     // (the forked path's batches of mostly small bodies)
     const u32 m0 = (blockIdx.x - big_blocks) * kWavesPerBlock + wv;
     const u32 step = small_stride ? small_stride * kWavesPerBlock : 0xffffffffu;
+    // message numbers [0, n_msgs); or, in walk order (forked path), positions
+    // [lo, hi) of walk_perm -- part 1 / 2 the larger / smaller bodies, 3 all
+    // of them
+    u32 lo = 0, n = n_msgs;
     if (walk_perm) {
-      // the messages in walk order (forked path): positions [lo, hi) of
-      // walk_perm -- part 1 / 2 the larger / smaller bodies, 3 all of them
       const u32 n_walk = walk_hist[2 * kWalkClasses];
       // (split_class bits 8-15: the first class another pass takes, whose
       // positions on are not executed here; no pass sets it now)
       const u32 tcls = split_class >> 8;
       const u32 split = walk_hist[kWalkClasses + (split_class & 0xffu)];
       const u32 t_hi = tcls ? walk_hist[kWalkClasses + tcls] : n_walk;
-      const u32 lo = walk_part == 2 ? split : 0u, hi = walk_part == 1 ? split : t_hi;
-      for (u32 i = m0; i < hi - lo; i = i + step < i ? 0xffffffffu : i + step) {
-        const u32 m = walk_perm[lo + i];
-        run(m, ring, pmap, sb, lane, status[m], 0u, 0u, out_len[m]);
-      }
-      return;
+      lo = walk_part == 2 ? split : 0u;
+      n = (walk_part == 1 ? split : t_hi) - lo;
     }
-    for (u32 m = m0; m < n_msgs; m = m + step < m ? 0xffffffffu : m + step)
-      if (in_len[m] <= big_threshold) run(m, ring, pmap, sb, lane, status[m], 0u, 0u, out_len[m]);
+    for (u32 i = m0; i < n; i = i + step < i ? 0xffffffffu : i + step) {
+      const u32 m = walk_perm ? walk_perm[lo + i] : i;
+      // (the walk order lists no large message: pass 1 sent those to pass 1b)
+      if (in_len[m] <= big_threshold) run(std::true_type{}, m, status[m], 0u, 0u, out_len[m]);
+    }
     return;
   }
   // large messages, listed by pass 1b: whole ones first (the longest start
@@ -173,21 +187,22 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) __attribute__((amdgpu_waves_pe
     const u32 got = atomicAdd(exec_next, lane == 0 ? 1u : 0u);
     const u32 idx = (u32)__builtin_amdgcn_readfirstlane((int)got);
     if (idx >= total) break;
+    // the message and its range: input from ip0, output [op0, op1)
+    u32 m, ip0 = 0, op0 = 0, op1;
     if (idx < n_whole) {
-      const u32 m = whole_list[idx];
-      run(m, ring, pmap, sb, lane, status[m], 0u, 0u, out_len[m]);
-      continue;
+      m = whole_list[idx];
+      op1 = out_len[m];
+    } else {
+      const u64 e = segs[idx - n_whole];
+      m = (u32)e;
+      if (m == 0xffffffffu) continue;  // a hole (the message runs whole)
+      const u32 k = (u32)(e >> 32) & 0x7fffffffu;
+      op0 = k << 16;
+      op1 = (e >> 63) ? out_len[m] : op0 + 65536u;
+      // segment k > 0 starts at the input offset pass 1b left in its slot
+      if (k) __builtin_memcpy(&ip0, out + out_off[m] + op0, 4);
     }
-    const u64 e = segs[idx - n_whole];
-    const u32 m = (u32)e;
-    if (m == 0xffffffffu) continue;  // a hole (the message runs whole)
-    const u32 k = (u32)(e >> 32) & 0x7fffffffu;
-    const u32 expected = out_len[m];
-    const u32 op0 = k << 16;
-    const u32 op1 = (e >> 63) ? expected : op0 + 65536u;
-    u32 ip0 = 0;  // segment k > 0 starts at the input offset pass 1b left in its slot
-    if (k) __builtin_memcpy(&ip0, out + out_off[m] + op0, 4);
-    run(m, ring, pmap, sb, lane, status[m], ip0, op0, op1);
+    run(std::false_type{}, m, status[m], ip0, op0, op1);
   }
 }
 
@@ -337,6 +352,9 @@ using ExecKernel = decltype(&exec_kernel<5>);
 // DESIGN.md section 5 were taken with exec_kernel<4>, <5> ahead of the
 // index_kernel instances in the code object.)
 ExecKernel exec_kernel_variant(int v) { return v == 4 ? &exec_kernel<4> : &exec_kernel<5>; }
+// exec_kernel's keep_hist argument: the general instance's kept history in
+// bits 0-15, the folded instance's in bits 16-31
+u32 exec_keep_arg(const DecodePlan& p) { return p.keep_hist | (p.keep_hist_whole << 16); }
 
 // One call's arrays: the caller's, and the workspace regions at the plan's
 // offsets.
@@ -425,7 +443,7 @@ hipError_t launch_big_exec(const DecodePlan& p, const DecodeBufs& b, hipStream_t
   b.ek<<<p.fork_big_blocks, kWavesPerBlock * 64, 0, st>>>(
       b.in, b.in_off, b.in_len, b.n_msgs, b.out, b.out_off, b.out_len, b.status, b.bm_base, b.bitmap,
       reinterpret_cast<const u32*>(s.seg_list), s.seg_count, s.whole_list, s.whole_count, s.exec_next,
-      p.fork_big_blocks, p.big_threshold, 0u, p.keep_hist, 0u, nullptr, nullptr, 0u, 0u);
+      p.fork_big_blocks, p.big_threshold, 0u, exec_keep_arg(p), 0u, nullptr, nullptr, 0u, 0u);
   return hipGetLastError();
 }
 
@@ -467,7 +485,7 @@ hipError_t launch_small(const DecodePlan& p, const DecodeBufs& b, hipStream_t st
   b.ek<<<p.small_grid, kWavesPerBlock * 64, 0, st>>>(
       b.in, b.in_off, b.in_len, b.n_msgs, b.out, b.out_off, b.out_len, b.status, b.bm_base, b.bitmap,
       reinterpret_cast<const u32*>(b.set0.seg_list), b.set0.seg_count, b.set0.whole_list, b.set0.whole_count,
-      b.set0.exec_next, 0u, p.big_threshold, 0u, p.keep_hist, p.small_stride, part ? b.walk_perm : nullptr,
+      b.set0.exec_next, 0u, p.big_threshold, 0u, exec_keep_arg(p), p.small_stride, part ? b.walk_perm : nullptr,
       part ? b.walk_hist : nullptr, part, p.split_class);
   return hipGetLastError();
 }
@@ -622,7 +640,7 @@ hipError_t launch_decode_v4(const u8* in, const u64* in_off, const u32* in_len,
     b.ek<<<p.big_blocks + p.small_blocks, kWavesPerBlock * 64, 0, stream>>>(
         in, in_off, in_len, n_msgs, out, out_off, out_len, status, b.bm_base, b.bitmap,
         reinterpret_cast<const u32*>(b.set0.seg_list), b.set0.seg_count, b.set0.whole_list, b.set0.whole_count,
-        b.set0.exec_next, p.big_blocks, p.big_threshold, p.prio, p.keep_hist, 0u, nullptr, nullptr, 0u, 0u);
+        b.set0.exec_next, p.big_blocks, p.big_threshold, p.prio, exec_keep_arg(p), 0u, nullptr, nullptr, 0u, 0u);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   fallback_kernel<<<p.fallback_grid, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_len, status,

@@ -145,7 +145,9 @@ int fsg_set_split_region_cap(uint32_t bytes);
  * paths read only this table, never the environment.  Names (values are
  * integers; -1 = the library's automatic rule where one exists):
  *   decode_fork (-1 | 0 | 1), split_walk (0..3), split_class, exec_keep
- *   (bytes of history at a window slide, 512..2000, multiple of 16),
+ *   (bytes of history at a window slide, 512..2000, multiple of 16; up to
+ *   3024 for the execution pass's 4 KiB-window instance, which a value
+ *   above 2000 sets alone),
  *   chunked_huge, small_persist, small_batch, split_huge, walk_order,
  *   lean_walk, exec_big_blocks, exec_prio, exec_big_blocks_fork, exec_pack,
  *   encode_wave_min, encode_wave_share, encode_wave_all_mb,

@@ -3,10 +3,13 @@ window and chunk rules over C3 messages and counts dependency rounds per group
 under several readiness / forwarding policies, so a restructuring can be priced
 before it is built.
 
-usage: python tools/exec_sim.py [n_msgs] [kind]     (kind 0 = C3 text)
+usage: python tools/exec_sim.py [n_msgs] [kind] [--window BYTES] [--keep BYTES]
+(kind 0 = C3 text; window and kept history at a slide default to the general
+instance's 3,072 / 1,024 -- the folded instance's window is 4,096)
 """
 from __future__ import annotations
 
+import argparse
 import sys
 from pathlib import Path
 
@@ -18,7 +21,7 @@ sys.path.insert(0, str(ROOT))
 import fsg  # noqa: E402
 from oracle.bind import Oracle  # noqa: E402  (test infrastructure: compresses the samples)
 
-WINDOW, KEEP, GROUP_BYTES = 3072, 1024, 1024
+GROUP_BYTES = 1024
 
 
 def pat_step(off):
@@ -62,8 +65,9 @@ def parse(comp: bytes):
     return tags
 
 
-def groups(tags):
-    """Yield (op, sbase, [(is_lit, len, src, t_op)]) per group as v5 forms them."""
+def groups(tags, window=3072, keep=1024):
+    """Yield (op, sbase, [(is_lit, len, src, t_op)]) per group as v5 forms them
+    in a window of `window` bytes that keeps `keep` bytes of history at a slide."""
     op, sbase = 0, -16 if False else 0
     i, n = 0, len(tags)
     while i < n:
@@ -84,8 +88,8 @@ def groups(tags):
             src = x if lit else t_op - x
             g.append((lit, ln, src, t_op))
             tot += ln
-        if op + tot - sbase > WINDOW:
-            sbase = (op - KEEP) & ~15
+        if op + tot - sbase > window:
+            sbase = (op - keep) & ~15
         yield op, sbase, g
         op += tot
         i += len(g)
@@ -202,15 +206,22 @@ def pat_src_span(c):
 
 
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-    kind = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("n_msgs", nargs="?", type=int, default=8)
+    ap.add_argument("kind", nargs="?", type=int, default=0)
+    ap.add_argument("--window", type=int, default=3072, help="LDS output window per wave, bytes")
+    ap.add_argument("--keep", type=int, default=1024, help="history kept when the window slides, bytes")
+    args = ap.parse_args()
+    if args.window % 16 or args.keep % 16 or not 512 <= args.keep <= ((args.window - 1024 - 48) & ~15):
+        ap.error("window and keep: multiples of 16, 512 <= keep <= (window - 1072) & ~15")
+    n, kind = args.n_msgs, args.kind
     b = fsg.make_batch(kind, np.full(n, 65536, np.uint32))
     orc = Oracle()
     st = dict(groups=0, tags=0, bytes=0, rw=0, act=0, rex=0, rfw=0, chunksA=0, chunksB=0, far=0)
     for i in range(n):
         comp = orc.compress(b.item(i))
         tags = parse(comp)
-        for op, sbase, g in groups(tags):
+        for op, sbase, g in groups(tags, args.window, args.keep):
             tc = chunks(op, sbase, g)
             st["groups"] += 1
             st["tags"] += len(g)
@@ -225,6 +236,7 @@ def main():
                     st["chunksA" if c[3] in "LF" else "chunksB"] += 1
                     st["far"] += c[3] == "F"
     G = st["groups"]
+    print(f"window {args.window} keep {args.keep}")
     print(f"msgs {n} groups {G} tags/group {st['tags']/G:.1f} bytes/group {st['bytes']/G:.0f}")
     print(f"chunks per group: round A {st['chunksA']/G:.1f} (far {st['far']/G:.1f}), rounds B {st['chunksB']/G:.1f}")
     print(f"rounds B per group: watermark {st['rw']/G:.2f} (lanes per round {st['act']/max(1,st['rw']):.1f}),"
