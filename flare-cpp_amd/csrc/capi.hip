@@ -85,6 +85,17 @@ constexpr bool encode_opts_defaults_ok() {
 }
 static_assert(fsg::kOptEncodeWaveMin == 14 && fsg::kOptEncodeWaveWg == 19 && encode_opts_defaults_ok(),
               "EncodeOpts defaults differ from the option table");
+// and Lz4Opts' (lz4_plan.h)
+constexpr bool lz4_opts_defaults_ok() {
+  constexpr fsg::Lz4Opts o;
+  const int64_t v[] = {o.lz4_big_min, o.lz4_encode_wave_min, o.lz4_encode_wave_per_cu, o.lz4f_force_serial,
+                       o.lz4f_block_wave_min, o.lz4f_nosize_fast, o.lz4f_length_wave_min, o.lz4f_linked_fast};
+  for (int i = fsg::kOptLz4BigMin; i <= fsg::kOptLz4fLinkedFast; ++i)
+    if (v[i - fsg::kOptLz4BigMin] != kOptDesc[i].dflt) return false;
+  return true;
+}
+static_assert(fsg::kOptLz4BigMin == 20 && fsg::kOptLz4fLinkedFast == 27 && lz4_opts_defaults_ok(),
+              "Lz4Opts defaults differ from the option table");
 static_assert(fsg::kEncRouteMain == FSG_PATH_MAIN && fsg::kEncRouteNoWorkspace == FSG_PATH_NO_WORKSPACE &&
                   fsg::kEncRouteForced == FSG_PATH_FORCED,
               "EncodeRoute differs from FSG_PATH_*");
@@ -97,6 +108,19 @@ std::atomic<int64_t> g_opt[fsg::kOptCount];
   }
   return true;
 }();
+// this call's LZ4 options
+fsg::Lz4Opts read_lz4_opts() {
+  fsg::Lz4Opts o;
+  o.lz4_big_min = fsg::opt(fsg::kOptLz4BigMin);
+  o.lz4_encode_wave_min = fsg::opt(fsg::kOptLz4EncodeWaveMin);
+  o.lz4_encode_wave_per_cu = fsg::opt(fsg::kOptLz4EncodeWavePerCu);
+  o.lz4f_force_serial = fsg::opt(fsg::kOptLz4fForceSerial);
+  o.lz4f_block_wave_min = fsg::opt(fsg::kOptLz4fBlockWaveMin);
+  o.lz4f_nosize_fast = fsg::opt(fsg::kOptLz4fNosizeFast);
+  o.lz4f_length_wave_min = fsg::opt(fsg::kOptLz4fLengthWaveMin);
+  o.lz4f_linked_fast = fsg::opt(fsg::kOptLz4fLinkedFast);
+  return o;
+}
 int find_opt(const char* name) {
   if (!name) return -1;
   for (int i = 0; i < fsg::kOptCount; ++i)
@@ -254,39 +278,18 @@ int decode_path(bool have_ws, size_t workspace_bytes, uint32_t n_msgs, uint32_t 
   return have_ws && workspace_bytes >= fsg::decode_v4_workspace_bytes(n_msgs, 0) ? FSG_PATH_MAIN
                                                                                  : FSG_PATH_NO_WORKSPACE;
 }
-bool lz4_two_pass(bool have_ws, size_t workspace_bytes, uint32_t n_msgs) {
-  return have_ws && workspace_bytes >= fsg::lz4_decode_workspace_bytes(n_msgs, 0);
+// The LZ4 calls and their reports: the call's plan (routes, sizes, launches;
+// lz4_plan.h, lz4_frame_plan.h) from the current options.
+// fsg_lz4_decompress_batch_ws: the two-pass decoder when p.two_pass and there
+// is a workspace; fsg_lz4_compress_batch: p.route, p.wave_min
+fsg::Lz4DecodePlan lz4_decode_plan(uint32_t n_msgs, size_t workspace_bytes) {
+  return fsg::lz4_decode_plan(n_msgs, workspace_bytes, 0, read_lz4_opts());
 }
-// fsg_lz4_compress_batch: path 0 = list + lanes + waves (a workspace of
-// fsg_lz4_compress_workspace_bytes), path 1 = the lanes alone on a workspace
-// of the earlier size.  *wave_min: bodies of at least this many bytes take
-// the wave encoder (fsg::kLz4WaveNone: none).
-// Automatic threshold, from the size matrix measured on MI355X (DESIGN.md
-// section 4, profiles/lz4wenc/): in batches of up to 256 bodies the wave
-// encoder was faster in every row, down to the smallest size measured (8 KiB);
-// at 65,536 bodies (C3) the lanes were twice as fast.  Nothing between was
-// measured, so batches over 256 bodies stay on the lanes.
-constexpr uint32_t kLz4WaveBatchMax = 256;
-constexpr fsg::u64 kLz4WaveMinSmallBatch = 8192;
-fsg::u64 lz4_encode_wave_min_auto(uint32_t n_msgs) {
-  return n_msgs <= kLz4WaveBatchMax ? kLz4WaveMinSmallBatch : fsg::kLz4WaveNone;
+fsg::Lz4EncodePlan lz4_encode_plan(uint32_t n_msgs, size_t workspace_bytes) {
+  return fsg::lz4_encode_plan(n_msgs, workspace_bytes, read_lz4_opts());
 }
-int lz4_encode_path(size_t workspace_bytes, uint32_t n_msgs, fsg::u64* wave_min) {
-  if (workspace_bytes < fsg::lz4_compress_workspace_bytes(n_msgs)) {
-    *wave_min = fsg::kLz4WaveNone;
-    return 1;
-  }
-  const int64_t v = fsg::opt(fsg::kOptLz4EncodeWaveMin);
-  *wave_min = v < 0 ? lz4_encode_wave_min_auto(n_msgs) : v >= 0xFFFFFFFFll ? fsg::kLz4WaveNone : (fsg::u64)v;
-  return 0;
-}
-// fsg_lz4f_compress_batch: the block encode's threshold, from option
-// lz4f_block_wave_min by the rule of lz4_encode_path; the automatic rule sees
-// the block entries of the workspace as its batch
-fsg::u64 lz4f_block_wave_min(uint32_t block_entries) {
-  const int64_t v = fsg::opt(fsg::kOptLz4fBlockWaveMin);
-  return v < 0 ? lz4_encode_wave_min_auto(block_entries) : v >= 0xFFFFFFFFll ? fsg::kLz4WaveNone : (fsg::u64)v;
-}
+// the reports state "none" as 0xFFFFFFFF
+uint64_t report_wave_min(fsg::u64 wave_min) { return wave_min < 0xFFFFFFFFull ? wave_min : 0xFFFFFFFFull; }
 }  // namespace
 
 size_t fsg_report_header_bytes(void) { return 256; }
@@ -342,12 +345,13 @@ int fsg_lz4_decompress_report(const void* header_host_copy, uint32_t n_msgs, siz
                               struct fsg_decode_report* out) {
   if (!out) return FSG_ERR_INVALID_ARG;
   *out = fsg_decode_report{};
-  if (!lz4_two_pass(workspace_bytes != 0, workspace_bytes, n_msgs)) {
+  const fsg::Lz4DecodePlan p = lz4_decode_plan(n_msgs, workspace_bytes);
+  if (workspace_bytes == 0 || !p.two_pass) {
     out->path = FSG_PATH_SINGLE_DESIGN;
     out->single_pass_messages = n_msgs;
     return FSG_SUCCESS;
   }
-  out->bitmap_words_capacity = fsg::lz4_decode_bitmap_capacity_words(n_msgs, workspace_bytes);
+  out->bitmap_words_capacity = p.cap_words;
   if (n_msgs == 0) return FSG_SUCCESS;
   if (!header_host_copy) return FSG_ERR_INVALID_ARG;
   fsg::DecodeHeaderCounts c;
@@ -363,9 +367,9 @@ int fsg_lz4_compress_report(const void* header_host_copy, uint32_t n_msgs, size_
                             struct fsg_lz4_encode_report* out) {
   if (!out) return FSG_ERR_INVALID_ARG;
   *out = fsg_lz4_encode_report{};
-  fsg::u64 wave_min;
-  out->path = (uint64_t)lz4_encode_path(workspace_bytes, n_msgs, &wave_min);
-  out->wave_min = wave_min < 0xFFFFFFFFull ? wave_min : 0xFFFFFFFFull;
+  const fsg::Lz4EncodePlan p = lz4_encode_plan(n_msgs, workspace_bytes);
+  out->path = (uint64_t)p.route;
+  out->wave_min = report_wave_min(p.wave_min);
   out->lane_messages = n_msgs;
   if (out->path != 0 || n_msgs == 0) return FSG_SUCCESS;
   if (!header_host_copy) return FSG_ERR_INVALID_ARG;
@@ -519,12 +523,12 @@ int fsg_lz4_compress_batch(const uint8_t* d_in, const uint64_t* d_in_off, const 
                            uint32_t n_msgs, uint8_t* d_out, const uint64_t* d_out_off, uint32_t* d_out_len,
                            int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream) {
   if (n_msgs && (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len || !d_status ||
-                 !d_workspace || workspace_bytes < fsg::lz4_compress_tables_bytes(n_msgs)))
+                 !d_workspace))
     return FSG_ERR_INVALID_ARG;
-  fsg::u64 wave_min;  // (the routing of fsg_lz4_compress_report)
-  (void)lz4_encode_path(workspace_bytes, n_msgs, &wave_min);
+  const fsg::Lz4EncodePlan p = lz4_encode_plan(n_msgs, workspace_bytes);  // (the routing of fsg_lz4_compress_report)
+  if (n_msgs && !p.valid) return FSG_ERR_INVALID_ARG;
   return record(fsg::launch_lz4_encode(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_len, d_status,
-                                       d_workspace, workspace_bytes, wave_min, (hipStream_t)stream),
+                                       d_workspace, (hipStream_t)stream, p),
                 "fsg_lz4_compress_batch");
 }
 
@@ -549,11 +553,12 @@ int fsg_lz4_decompress_batch_ws(const uint8_t* d_in, const uint64_t* d_in_off, c
   if (n_msgs && (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status))
     return FSG_ERR_INVALID_ARG;
   // no usable workspace: the one-pass lane kernel (same results)
-  if (!lz4_two_pass(d_workspace != nullptr, workspace_bytes, n_msgs))
+  const fsg::Lz4DecodePlan p = lz4_decode_plan(n_msgs, workspace_bytes);
+  if (!d_workspace || !p.two_pass)
     return fsg_lz4_decompress_batch(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
                                     d_status, stream);
   return record(fsg::launch_lz4_decode2(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
-                                        d_status, d_workspace, workspace_bytes, (hipStream_t)stream, nullptr),
+                                        d_status, d_workspace, (hipStream_t)stream, nullptr, p),
                 "fsg_lz4_decompress_batch_ws");
 }
 
@@ -563,7 +568,8 @@ int fsg_lz4_decompress_batch_2s(const uint8_t* d_in, const uint64_t* d_in_off, c
                                 void* d_workspace, size_t workspace_bytes, void* stream, void* pass1_stream) {
   if (n_msgs && (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status))
     return FSG_ERR_INVALID_ARG;
-  if (!lz4_two_pass(d_workspace != nullptr, workspace_bytes, n_msgs)) {
+  const fsg::Lz4DecodePlan p = lz4_decode_plan(n_msgs, workspace_bytes);
+  if (!d_workspace || !p.two_pass) {
     // the one-pass kernel on `stream`, ordered behind pass1_stream's work
     if (pass1_stream && pass1_stream != stream) {
       const hipError_t e = fsg::order_after((hipStream_t)stream, (hipStream_t)pass1_stream);
@@ -573,8 +579,7 @@ int fsg_lz4_decompress_batch_2s(const uint8_t* d_in, const uint64_t* d_in_off, c
                                     d_status, stream);
   }
   return record(fsg::launch_lz4_decode2(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
-                                        d_status, d_workspace, workspace_bytes, (hipStream_t)stream,
-                                        (hipStream_t)pass1_stream),
+                                        d_status, d_workspace, (hipStream_t)stream, (hipStream_t)pass1_stream, p),
                 "fsg_lz4_decompress_batch_2s");
 }
 
@@ -613,11 +618,10 @@ int fsg_lz4f_compress_batch_flags(const uint8_t* d_in, const uint64_t* d_in_off,
   if (n_msgs == 0) return FSG_SUCCESS;
   if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len || !d_status || !d_workspace)
     return FSG_ERR_INVALID_ARG;
-  const fsg::u32 entries = fsg::lz4f_compress_block_capacity(n_msgs, workspace_bytes, block_size_id);
-  if (entries == 0) return FSG_ERR_INVALID_ARG;
+  const fsg::Lz4fEncodePlan p = fsg::lz4f_encode_plan(n_msgs, workspace_bytes, block_size_id, read_lz4_opts());
+  if (!p.valid) return FSG_ERR_INVALID_ARG;
   return record(fsg::launch_lz4f_encode(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_len, d_status,
-                                        block_size_id, flags, d_workspace, workspace_bytes,
-                                        lz4f_block_wave_min(entries), (hipStream_t)stream),
+                                        block_size_id, flags, d_workspace, (hipStream_t)stream, p),
                 "fsg_lz4f_compress_batch");
 }
 
@@ -643,15 +647,10 @@ int fsg_lz4f_decompress_batch(const uint8_t* d_in, const uint64_t* d_in_off, con
   if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status ||
       !d_workspace)
     return FSG_ERR_INVALID_ARG;
-  const fsg::u32 entries = fsg::lz4f_decompress_block_capacity(n_msgs, workspace_bytes);
-  if (entries == 0) return FSG_ERR_INVALID_ARG;
+  const fsg::Lz4fDecodePlan p = fsg::lz4f_decode_plan(n_msgs, workspace_bytes, read_lz4_opts());
+  if (!p.valid) return FSG_ERR_INVALID_ARG;
   return record(fsg::launch_lz4f_decode(d_in, d_in_off, d_in_len, n_msgs, d_out, d_out_off, d_out_cap, d_out_len,
-                                        d_status, d_workspace, workspace_bytes,
-                                        fsg::opt(fsg::kOptLz4fForceSerial) != 0,
-                                        fsg::opt(fsg::kOptLz4fNosizeFast) != 0,
-                                        fsg::opt(fsg::kOptLz4fLinkedFast) != 0,
-                                        fsg::lz4f_length_wave_min(fsg::opt(fsg::kOptLz4fLengthWaveMin)),
-                                        (hipStream_t)stream),
+                                        d_status, d_workspace, (hipStream_t)stream, p),
                 "fsg_lz4f_decompress_batch");
 }
 
@@ -660,11 +659,10 @@ int fsg_lz4f_decoded_lengths_batch(const uint8_t* d_in, const uint64_t* d_in_off
                                    size_t workspace_bytes, void* stream) {
   if (n_msgs == 0) return FSG_SUCCESS;
   if (!d_in || !d_in_off || !d_in_len || !d_length || !d_status || !d_workspace) return FSG_ERR_INVALID_ARG;
-  const fsg::u32 entries = fsg::lz4f_decompress_block_capacity(n_msgs, workspace_bytes);
-  if (entries == 0) return FSG_ERR_INVALID_ARG;
-  return record(fsg::launch_lz4f_decoded_lengths(
-                    d_in, d_in_off, d_in_len, n_msgs, d_length, d_status, d_workspace, workspace_bytes,
-                    fsg::lz4f_length_wave_min(fsg::opt(fsg::kOptLz4fLengthWaveMin)), (hipStream_t)stream),
+  const fsg::Lz4fDecodePlan p = fsg::lz4f_decode_plan(n_msgs, workspace_bytes, read_lz4_opts());
+  if (!p.valid) return FSG_ERR_INVALID_ARG;
+  return record(fsg::launch_lz4f_decoded_lengths(d_in, d_in_off, d_in_len, n_msgs, d_length, d_status, d_workspace,
+                                                 (hipStream_t)stream, p),
                 "fsg_lz4f_decoded_lengths_batch");
 }
 
@@ -841,10 +839,10 @@ int fsg_lz4f_compress_report(const void* header_host_copy, uint32_t n_msgs, size
   if (!out || block_size_id < 4 || block_size_id > 7) return FSG_ERR_INVALID_ARG;
   *out = fsg_lz4f_encode_report{};
   if (n_msgs == 0) return FSG_SUCCESS;
-  out->block_entries = fsg::lz4f_compress_block_capacity(n_msgs, workspace_bytes, block_size_id);
-  if (out->block_entries == 0 || !header_host_copy) return FSG_ERR_INVALID_ARG;
-  const fsg::u64 wave_min = lz4f_block_wave_min((uint32_t)out->block_entries);
-  out->block_wave_min = wave_min < 0xFFFFFFFFull ? wave_min : 0xFFFFFFFFull;
+  const fsg::Lz4fEncodePlan p = fsg::lz4f_encode_plan(n_msgs, workspace_bytes, block_size_id, read_lz4_opts());
+  out->block_entries = p.valid ? p.w.nb_cap : 0;
+  if (!p.valid || !header_host_copy) return FSG_ERR_INVALID_ARG;
+  out->block_wave_min = report_wave_min(p.inner.wave_min);
   fsg::Lz4fEncodeHeaderCounts c;
   fsg::lz4f_encode_header_counts(header_host_copy, &c);
   out->blocks = c.blocks;
@@ -858,8 +856,9 @@ int fsg_lz4f_decompress_report(const void* header_host_copy, uint32_t n_msgs, si
   if (!out) return FSG_ERR_INVALID_ARG;
   *out = fsg_lz4f_decode_report{};
   if (n_msgs == 0) return FSG_SUCCESS;
-  out->block_entries = fsg::lz4f_decompress_block_capacity(n_msgs, workspace_bytes);
-  if (out->block_entries == 0 || !header_host_copy) return FSG_ERR_INVALID_ARG;
+  const fsg::Lz4fDecodePlan p = fsg::lz4f_decode_plan(n_msgs, workspace_bytes, read_lz4_opts());
+  out->block_entries = p.valid ? p.w.nb_cap : 0;
+  if (!p.valid || !header_host_copy) return FSG_ERR_INVALID_ARG;
   fsg::Lz4fDecodeHeaderCounts c;
   fsg::lz4f_decode_header_counts(header_host_copy, &c);
   out->fast_messages = c.fast_messages;

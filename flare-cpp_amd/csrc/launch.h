@@ -7,6 +7,7 @@
 
 #include "decode_v4_plan.h"  // decode_v4_workspace_bytes, decode_v4_bitmap_capacity_words (inline)
 #include "encode_v3_plan.h"
+#include "lz4_frame_plan.h"  // and lz4_plan.h: the LZ4 sizes, options and plans (inline)
 #include "snappy_device.h"
 
 namespace fsg {
@@ -52,14 +53,11 @@ hipError_t launch_pack(const u8* src, const u64* src_off, const u32* len, const 
                        u8* dst, u64* pack_off, u64* total, void* ws, hipStream_t stream);
 
 // ---- LZ4
-// LZ4 compress (lz4_encode_wave.hip): bodies of at least wave_min bytes go to
-// the wave encoder; kLz4WaveNone = none do
-constexpr u64 kLz4WaveNone = 1ull << 32;
-size_t lz4_compress_workspace_bytes(u32 n_msgs);
-size_t lz4_compress_tables_bytes(u32 n_msgs);  // the lanes' tables alone: the workspace before the wave encoder
+// (lz4_plan.h: lz4_compress_workspace_bytes, lz4_decode_workspace_bytes, lz4_encode_plan and lz4_decode_plan, inline)
+// LZ4 compress (lz4_encode_wave.hip): bodies of at least p.wave_min bytes go to the wave encoder
 hipError_t launch_lz4_encode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
-                             const u64* out_off, u32* out_len, i32* status, void* ws, size_t ws_bytes, u64 wave_min,
-                             hipStream_t stream);
+                             const u64* out_off, u32* out_len, i32* status, void* ws, hipStream_t stream,
+                             const Lz4EncodePlan& p);
 hipError_t launch_lz4_encode_lanes(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                                    const u64* out_off, u32* out_len, i32* status, void* tables, u64 wave_min,
                                    hipStream_t stream);
@@ -69,8 +67,6 @@ hipError_t launch_lz4_decode(const u8* in, const u64* in_off, const u32* in_len,
 hipError_t launch_lz4_decode_fallback(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                                       const u64* out_off, const u32* out_cap, u32* out_len, i32* status,
                                       u32* fb_count, hipStream_t stream);
-size_t lz4_decode_workspace_bytes(u32 n_msgs, u64 total_in_bytes);
-u64 lz4_decode_bitmap_capacity_words(u32 n_msgs, size_t ws_bytes);
 // Entries that continue earlier output (the blocks of a linked LZ4 frame).
 // word[e] >> shift bytes directly below entry e's slot are its history: the
 // index passes accept offsets into them.  An entry with a bit of chained_mask
@@ -91,32 +87,25 @@ struct Lz4Chains {
 // chains = nullptr: no entry has a prefix (the forms of the kernels without one)
 hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
-                              size_t ws_bytes, hipStream_t stream, hipStream_t pass1_stream,
+                              hipStream_t stream, hipStream_t pass1_stream, const Lz4DecodePlan& p,
                               const Lz4Chains* chains = nullptr);
 
 // ---- LZ4 frames (lz4_frame.hip; include/flare_lz4_gpu.h, "LZ4 frames").  The
 // calls get no input size: the workspace says what it was sized for, and the
-// *_block_capacity functions give the block entries it holds (0: too small).
-size_t lz4f_compress_workspace_bytes(u32 n_msgs, u64 total_in_bytes, u32 block_size_id);
-size_t lz4f_decompress_workspace_bytes(u32 n_msgs, u64 total_in_bytes);
-u32 lz4f_compress_block_capacity(u32 n_msgs, size_t ws_bytes, u32 block_size_id);
-u32 lz4f_decompress_block_capacity(u32 n_msgs, size_t ws_bytes);
+// plan's w.nb_cap gives the block entries it holds (lz4_frame_plan.h:
+// lz4f_*_workspace_bytes, lz4f_encode_plan and lz4f_decode_plan, inline).
 hipError_t launch_lz4f_encode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, u32* out_len, i32* status, u32 block_size_id, u32 flags, void* ws,
-                              size_t ws_bytes, u64 wave_min, hipStream_t stream);
+                              hipStream_t stream, const Lz4fEncodePlan& p);
 // fsg_lz4f_xxh32_batch: XXH32 of each body on the checksum kernel (lz4f_xxh.h), no workspace
 hipError_t launch_lz4f_xxh32(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u32 seed, u32* xxh,
                              hipStream_t stream);
 hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
-                              size_t ws_bytes, bool force_serial, bool nosize_fast, bool linked_fast,
-                              u32 length_wave_min, hipStream_t stream);
-// the length pass's wave threshold from option lz4f_length_wave_min (-1: the automatic rule)
-u32 lz4f_length_wave_min(i64 option);
+                              hipStream_t stream, const Lz4fDecodePlan& p);
 // fsg_lz4f_decoded_lengths_batch: on a decompress workspace
 hipError_t launch_lz4f_decoded_lengths(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* lengths,
-                                       i32* status, void* ws, size_t ws_bytes, u32 length_wave_min,
-                                       hipStream_t stream);
+                                       i32* status, void* ws, hipStream_t stream, const Lz4fDecodePlan& p);
 hipError_t launch_lz4f_content_sizes(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* sizes,
                                      i32* status, hipStream_t stream);
 

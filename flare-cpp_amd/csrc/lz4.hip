@@ -17,7 +17,7 @@
 // so the decode walk is serial per message like Snappy's; the encoder is a
 // serial greedy chain.  Position tables live in the workspace (16 KiB per
 // message), zeroed by the launch.  Compress also has a wave per body for the
-// large ones: lz4_encode_wave.hip, which holds the call's routing.
+// large ones: lz4_encode_wave.hip; the call's routing is lz4_plan.h's.
 #include "launch.h"
 #include "snappy_device.h"
 

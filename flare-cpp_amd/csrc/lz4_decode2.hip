@@ -54,7 +54,6 @@
 
 #include "launch.h"
 #include "launch_util.h"
-#include "options.h"
 #include "wave_util.h"
 
 namespace fsg {
@@ -82,8 +81,7 @@ constexpr u32 kL4BitGroups = 4;    // per-lane ring of 128-byte bit groups (4 wo
 constexpr u32 kL4BitWords = 4 * kL4BitGroups;
 constexpr i32 kL4Parsing = -1;
 
-// ---- pass 2 geometry
-constexpr u32 kL4Waves = 4;                   // waves per block
+// ---- pass 2 geometry (kL4Waves, the waves per block: lz4_plan.h)
 // The ring is refilled while it holds fewer than kL4RefillBelow positions; a
 // fill adds <= 512 bits = <= 342 positions (two per three bytes).  With 1,024
 // positions and a refill below 260, the next group's prefetch (issued at the
@@ -1228,23 +1226,7 @@ extern "C" int fsg_debug_l4stamps(unsigned long long* out, int reset) {
 }
 #endif
 
-// Workspace: [0, 256) counters (0 bitmap words allocated, 1 large blocks
-// listed, 2 large blocks taken) | bm_base[n] | hdr[n] | big_list[n] | bitmap
-// words (round_up(ceil(block / 32), 4) per message <= total / 32 + 4 n).
-// Counter 3: the messages the one-pass lane kernel finished as this launch's
-// fallback (path report, fsg_lz4_decompress_report).
-constexpr u64 kL4Head = 256;
-constexpr u32 kL4CtrFallback = 3;
-__host__ u64 l4_list_bytes(u32 n) { return ((u64)n * 4 + 255) & ~(u64)255; }
-size_t lz4_decode_workspace_bytes(u32 n_msgs, u64 total_in_bytes) {
-  return kL4Head + 3 * l4_list_bytes(n_msgs) + 4 * (total_in_bytes / 32 + 4 * (u64)n_msgs + 4);
-}
-// Bitmap capacity in words (whole 16-byte groups) of a workspace of at least
-// lz4_decode_workspace_bytes(n_msgs, 0) bytes; shared by the launch and the
-// path report.
-u64 lz4_decode_bitmap_capacity_words(u32 n_msgs, size_t ws_bytes) {
-  return (ws_bytes - (kL4Head + 3 * l4_list_bytes(n_msgs))) / 16 * 4;
-}
+// (workspace layout, kL4Head, kL4CtrFallback and the big_min rule: lz4_plan.h)
 void lz4_decode_header_counts(const void* header, DecodeHeaderCounts* c) {
   u32 ctr[kL4CtrFallback + 1];
   __builtin_memcpy(ctr, header, sizeof(ctr));
@@ -1253,11 +1235,6 @@ void lz4_decode_header_counts(const void* header, DecodeHeaderCounts* c) {
   c->large = ctr[1];
   c->fallback = c->fallback_bitmap = ctr[kL4CtrFallback];  // the only cause
 }
-// blocks above this many bytes take the wave walk (FSG_L4_BIG_MIN, read per
-// call: the tests lower it)
-constexpr u32 kL4BigMin = 65536;
-constexpr u32 kL4SmallBatch = 256;
-constexpr u32 kL4BigMinSmall = 2048;
 
 // Per-device event that orders the execution pass behind the index pass in
 // the two-stream form (created on first use; nullptr: one stream).
@@ -1270,13 +1247,13 @@ bool create_l4_two(L4Two* t) { return hipEventCreateWithFlags(&t->pass1, hipEven
 L4Two* l4_two() { return per_device<L4Two>(create_l4_two); }
 }  // namespace
 
+// every size and decision from lz4_decode_plan (lz4_plan.h)
 hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
-                              size_t ws_bytes, hipStream_t stream, hipStream_t pass1_stream,
+                              hipStream_t stream, hipStream_t pass1_stream, const Lz4DecodePlan& p,
                               const Lz4Chains* chains) {
   if (n_msgs == 0) return hipSuccess;
-  const u64 fixed = kL4Head + 3 * l4_list_bytes(n_msgs);
-  if (ws_bytes < fixed) return hipErrorInvalidValue;
+  if (!p.valid) return hipErrorInvalidValue;
   // Two-stream form (as launch_decode_v4's): the index pass on pass1_stream,
   // the execution and fallback passes on `stream` behind an event, so a
   // caller's next batch walks while this one executes
@@ -1288,37 +1265,29 @@ hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len
   }
   u8* w = static_cast<u8*>(ws);
   u32* counter = reinterpret_cast<u32*>(w);
-  u32* bm_base = reinterpret_cast<u32*>(w + kL4Head);
-  u32* hdr = reinterpret_cast<u32*>(w + kL4Head + l4_list_bytes(n_msgs));
-  u32* big_list = reinterpret_cast<u32*>(w + kL4Head + 2 * l4_list_bytes(n_msgs));
-  u32* bitmap = reinterpret_cast<u32*>(w + fixed);
-  // a batch of at most kL4SmallBatch messages has the chip to itself: a
-  // wave per block is quicker than one lane per block from a few KiB on
-  // (option lz4_big_min overrides, -1 = this rule)
-  const i64 bm_opt = opt(kOptLz4BigMin);
-  const u32 big_min = bm_opt >= 0 && bm_opt <= 0xffffffffll ? (u32)bm_opt
-                                                            : (n_msgs <= kL4SmallBatch ? kL4BigMinSmall : kL4BigMin);
-  const u64 cap_words = lz4_decode_bitmap_capacity_words(n_msgs, ws_bytes);
+  u32* bm_base = reinterpret_cast<u32*>(w + p.bm_base);
+  u32* hdr = reinterpret_cast<u32*>(w + p.hdr);
+  u32* big_list = reinterpret_cast<u32*>(w + p.big_list);
+  u32* bitmap = reinterpret_cast<u32*>(w + p.bitmap);
   e = hipMemsetAsync(counter, 0, kL4Head, s1);
   if (e != hipSuccess) return e;
   // (no chains: the forms without a prefix, the code the block calls always ran)
   if (chains)
-    lz4_index_kernel<true><<<(n_msgs + 63) / 64, 64, 0, s1>>>(in, in_off, in_len, n_msgs, out_cap, out_len, status,
-                                                              counter, bm_base, hdr, bitmap, cap_words, big_list,
-                                                              big_min, chains->word, chains->shift);
+    lz4_index_kernel<true><<<p.index_grid, 64, 0, s1>>>(in, in_off, in_len, n_msgs, out_cap, out_len, status, counter,
+                                                        bm_base, hdr, bitmap, p.cap_words, big_list, p.big_min,
+                                                        chains->word, chains->shift);
   else
-    lz4_index_kernel<false><<<(n_msgs + 63) / 64, 64, 0, s1>>>(in, in_off, in_len, n_msgs, out_cap, out_len, status,
-                                                               counter, bm_base, hdr, bitmap, cap_words, big_list,
-                                                               big_min, nullptr, 0);
+    lz4_index_kernel<false><<<p.index_grid, 64, 0, s1>>>(in, in_off, in_len, n_msgs, out_cap, out_len, status, counter,
+                                                         bm_base, hdr, bitmap, p.cap_words, big_list, p.big_min,
+                                                         nullptr, 0);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  // (a grid of 256 blocks: with no listed block each wave reads the count and leaves)
   if (chains)
-    lz4_index_big_kernel<true><<<256, kBigWaves * 64, 0, s1>>>(in, in_off, in_len, out_len, status, counter, big_list,
-                                                               bm_base, hdr, bitmap, chains->word, chains->shift);
+    lz4_index_big_kernel<true><<<p.index_big_grid, kBigWaves * 64, 0, s1>>>(
+        in, in_off, in_len, out_len, status, counter, big_list, bm_base, hdr, bitmap, chains->word, chains->shift);
   else
-    lz4_index_big_kernel<false><<<256, kBigWaves * 64, 0, s1>>>(in, in_off, in_len, out_len, status, counter, big_list,
-                                                                bm_base, hdr, bitmap, nullptr, 0);
+    lz4_index_big_kernel<false><<<p.index_big_grid, kBigWaves * 64, 0, s1>>>(
+        in, in_off, in_len, out_len, status, counter, big_list, bm_base, hdr, bitmap, nullptr, 0);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (two) {
@@ -1327,17 +1296,17 @@ hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len
     if ((e = hipStreamWaitEvent(stream, two->pass1, 0)) != hipSuccess) return e;
   }
   if (chains)
-    lz4_exec_kernel<true><<<(n_msgs + kL4Waves - 1) / kL4Waves, kL4Waves * 64, 0, stream>>>(
-        in, in_off, in_len, n_msgs, out, out_off, out_len, status, bm_base, hdr, bitmap, chains->word,
-        chains->chained_mask);
+    lz4_exec_kernel<true><<<p.exec_grid, kL4Waves * 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_len,
+                                                                     status, bm_base, hdr, bitmap, chains->word,
+                                                                     chains->chained_mask);
   else
-    lz4_exec_kernel<false><<<(n_msgs + kL4Waves - 1) / kL4Waves, kL4Waves * 64, 0, stream>>>(
-        in, in_off, in_len, n_msgs, out, out_off, out_len, status, bm_base, hdr, bitmap, nullptr, 0);
+    lz4_exec_kernel<false><<<p.exec_grid, kL4Waves * 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_len,
+                                                                      status, bm_base, hdr, bitmap, nullptr, 0);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if (chains && chains->n_chains) {
-    lz4_exec_chain_kernel<<<(chains->n_chains + kL4Waves - 1) / kL4Waves, kL4Waves * 64, 0, stream>>>(
-        in, in_off, in_len, n_msgs, out, out_off, out_len, status, bm_base, hdr, bitmap, *chains);
+  if (chains && p.chain_grid) {
+    lz4_exec_chain_kernel<<<p.chain_grid, kL4Waves * 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_len,
+                                                                      status, bm_base, hdr, bitmap, *chains);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

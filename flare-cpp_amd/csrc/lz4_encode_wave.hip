@@ -34,7 +34,6 @@
 // 0); literal copies read the body's own bytes.  Every store is exact-length
 // inside the body's slot.  CPU model, checked block for block against the
 // oracle: tools/l4wenc_model.cc.
-#include "options.h"
 #include "launch.h"
 #include "snappy_device.h"
 
@@ -45,19 +44,13 @@ namespace {
 constexpr u32 kMinMatch = 4, kMfLimit = 12, kLastLiterals = 5, kHashLog = 12, kSkipTrigger = 6;
 constexpr u32 kDistanceMax = 65535, kLimit64K = 65536 + kMfLimit - 1;
 constexpr u32 kMaxInput = 0x7E000000u;  // LZ4_MAX_INPUT_SIZE
-constexpr u32 kTableBytes = 16384;      // 8,192 x u16 or 4,096 x u32
+constexpr u32 kTableBytes = kLz4EncTableBytes;  // 8,192 x u16 or 4,096 x u32
 
-// ---- workspace of the routed call: header, list, then the lanes' tables
-constexpr u32 kHead = 256;
+// ---- the header of the routed call's workspace (its layout: lz4_plan.h)
 constexpr u32 kCtrListed = 0;  // bodies on the list
 constexpr u32 kCtrNext = 1;    // the wave kernel's work counter
 constexpr u32 kCtrDone = 2;    // bodies the wave kernel encoded
 constexpr u32 kCtrBytes = 4;   // their input bytes (u64: words 4, 5)
-constexpr u32 kCus = 256, kCuLds = 160 * 1024;
-// one-wave workgroups of 16 KiB: nine fit beside the CU's other allocations
-constexpr u32 kWavesPerCu = kCuLds / kTableBytes - 1;
-
-__host__ __device__ inline size_t list_bytes(u32 n_msgs) { return ((size_t)n_msgs * 4 + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ u32 rl(u32 v, u32 l) { return (u32)__builtin_amdgcn_readlane((int)v, (int)l); }
 __device__ __forceinline__ u32 rfl(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
@@ -354,10 +347,6 @@ __global__ __launch_bounds__(64) void lz4_encode_wave_kernel(const u8* __restric
 
 }  // namespace
 
-// ---- routing (capi.hip: fsg_lz4_compress_batch and fsg_lz4_compress_report)
-size_t lz4_compress_workspace_bytes(u32 n_msgs) { return kHead + list_bytes(n_msgs) + (size_t)n_msgs * kTableBytes; }
-size_t lz4_compress_tables_bytes(u32 n_msgs) { return (size_t)n_msgs * kTableBytes; }
-
 void lz4_encode_header_counts(const void* header, Lz4EncodeHeaderCounts* c) {
   u32 ctr[kCtrBytes + 2];
   __builtin_memcpy(ctr, header, sizeof(ctr));
@@ -366,39 +355,30 @@ void lz4_encode_header_counts(const void* header, Lz4EncodeHeaderCounts* c) {
   c->wave_bytes = (u64)ctr[kCtrBytes] | (u64)ctr[kCtrBytes + 1] << 32;
 }
 
-// fsg_lz4_compress_batch.  A workspace of lz4_compress_workspace_bytes: header,
-// list, tables; the bodies of at least wave_min bytes on the wave encoder, the
-// others on the lanes, both on `stream`.  A workspace of the earlier size
-// (the tables alone): the lanes only, as before the wave encoder.  Either way
-// the launch zeroes what it uses.
+// fsg_lz4_compress_batch, every size and decision from lz4_encode_plan
+// (lz4_plan.h).  Route 0: the bodies of at least wave_min bytes on the wave
+// encoder, the others on the lanes, both on `stream`.  Route 1: the lanes
+// only, as before the wave encoder.  Either way the launch zeroes what it
+// uses.
 hipError_t launch_lz4_encode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
-                             const u64* out_off, u32* out_len, i32* status, void* ws, size_t ws_bytes, u64 wave_min,
-                             hipStream_t stream) {
+                             const u64* out_off, u32* out_len, i32* status, void* ws, hipStream_t stream,
+                             const Lz4EncodePlan& p) {
   if (n_msgs == 0) return hipSuccess;
-  const bool routed = ws_bytes >= lz4_compress_workspace_bytes(n_msgs);
-  hipError_t e = hipMemsetAsync(ws, 0, routed ? lz4_compress_workspace_bytes(n_msgs) : lz4_compress_tables_bytes(n_msgs),
-                                stream);
+  hipError_t e = hipMemsetAsync(ws, 0, p.zero_bytes, stream);
   if (e != hipSuccess) return e;
-  if (!routed)
-    return launch_lz4_encode_lanes(in, in_off, in_len, n_msgs, out, out_off, out_len, status, ws, kLz4WaveNone, stream);
-  u8* const tables = static_cast<u8*>(ws) + kHead + list_bytes(n_msgs);
-  if (wave_min >= kLz4WaveNone)
+  u8* const tables = static_cast<u8*>(ws) + p.tables_off;
+  if (p.wave_min >= kLz4WaveNone)
     return launch_lz4_encode_lanes(in, in_off, in_len, n_msgs, out, out_off, out_len, status, tables, kLz4WaveNone,
                                    stream);
   u32* hdr = static_cast<u32*>(ws);
-  u32* list = reinterpret_cast<u32*>(static_cast<u8*>(ws) + kHead);
-  lz4_encode_list_kernel<<<(n_msgs + 255) / 256, 256, 0, stream>>>(in_len, n_msgs, wave_min, hdr, list);
+  u32* list = reinterpret_cast<u32*>(static_cast<u8*>(ws) + p.list_off);
+  lz4_encode_list_kernel<<<p.list_grid, 256, 0, stream>>>(in_len, n_msgs, p.wave_min, hdr, list);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  // resident waves: an upper bound (LDS: 16 KiB a wave); waves past the list leave at once
-  const i64 pc = opt(kOptLz4EncodeWavePerCu);
-  const u32 per_cu = pc > 0 && pc < (i64)kWavesPerCu ? (u32)pc : kWavesPerCu;
-  const u32 waves = kCus * per_cu;
-  lz4_encode_wave_kernel<<<n_msgs < waves ? n_msgs : waves, 64, 0, stream>>>(in, in_off, in_len, out, out_off, out_len,
-                                                                              status, hdr, list);
+  lz4_encode_wave_kernel<<<p.wave_grid, 64, 0, stream>>>(in, in_off, in_len, out, out_off, out_len, status, hdr, list);
   e = hipGetLastError();
-  if (e != hipSuccess || wave_min == 0) return e;  // (0: no body is left for the lanes)
-  return launch_lz4_encode_lanes(in, in_off, in_len, n_msgs, out, out_off, out_len, status, tables, wave_min, stream);
+  if (e != hipSuccess || p.wave_min == 0) return e;  // (0: no body is left for the lanes)
+  return launch_lz4_encode_lanes(in, in_off, in_len, n_msgs, out, out_off, out_len, status, tables, p.wave_min, stream);
 }
 
 }  // namespace fsg

@@ -7,8 +7,10 @@
 // lz4_decode2.hip) run a frame's blocks as if they were messages; the kernels
 // here only cut messages into blocks and put frames together (compress), or
 // take frames apart and judge the result (decompress).  Those launches are
-// called as they are; launch_lz4_decode2 alone takes one more argument, for
-// the linked frames below.
+// called as they are, on the plans the frame's plan holds for them;
+// launch_lz4_decode2 alone takes one more argument, for the linked frames
+// below.  Workspace layouts, capacities, thresholds and grid sizes:
+// lz4_frame_plan.h (tests/cpp/test_lz4_plan.cc).
 //
 // Compress: plan (a lane per message: its blocks' columns, staging slots from
 // two counters) -> launch_lz4_encode on the block columns -> XXH32 of the
@@ -68,7 +70,6 @@ constexpr u32 kFdLkMsgs = 16, kFdLkBlocks = 17;  // answered by the fast route f
 // listed block entries with a checksum, pending frames with a content
 // checksum: 0 lets the checksum kernels leave at once
 constexpr u32 kFdSumBlocks = 18, kFdSumMsgs = 19;
-constexpr u64 kHead = 256;
 
 // msg_route values
 constexpr u32 kRouteDone = 0, kRouteFast = 1, kRouteLinked = 2, kRouteNoSize = 3, kRouteRejected = 4,
@@ -89,14 +90,7 @@ constexpr u32 kBlkPrefixShift = 16;
 
 constexpr u32 kNoFit = 0xFFFFFFFFu;
 
-__host__ __device__ inline u64 round_up(u64 v, u64 a) { return (v + a - 1) / a * a; }
-
-// staging slot of a block of L input bytes in the compressor: the body bound
-// of the block codec (fsg_lz4_max_compressed_length), 16-byte aligned, and 64
-// spare bytes
-__host__ __device__ inline u64 enc_slot(u64 L) { return round_up(5 + L + L / 255 + 16, 16) + 64; }
-// and of a stored block of sz bytes in the decompressor: varint32 + bytes
-__host__ __device__ inline u64 dec_slot(u64 sz) { return round_up(5 + sz, 16) + 16; }
+// (the staging slots of a block, enc_slot and dec_slot: lz4_frame_plan.h)
 
 __device__ __forceinline__ u32 wave_scan(u32 v) { return wave_incl_scan(v); }
 
@@ -130,7 +124,6 @@ struct BlockCols {
   u32* src_len;  // decompress: stored size
   u32* flags;
 };
-constexpr u64 kBlockColBytes = 3 * 8 + 6 * 4;
 
 struct MsgCols {
   u32* route;
@@ -838,115 +831,32 @@ __global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ 
   }
 }
 
-// ---- workspace layouts
-u64 list_bytes(u64 n) { return round_up(n * 4, 256); }
-
+// ---- the columns in a workspace (offsets and sizes: lz4_frame_plan.h)
 MsgCols msg_cols(u8* w, u32 n_msgs) {
   MsgCols mc;
-  const u64 lb = list_bytes(n_msgs);
+  const u64 lb = lz4f_list_bytes(n_msgs);
   mc.route = reinterpret_cast<u32*>(w);
   mc.first = reinterpret_cast<u32*>(w + lb);
   mc.nb = reinterpret_cast<u32*>(w + 2 * lb);
   mc.xxh = reinterpret_cast<u32*>(w + 3 * lb);
   return mc;
 }
-u64 block_cols_bytes(u64 nb) { return round_up(nb * kBlockColBytes, 256); }
 BlockCols block_cols(u8* w, u64 nb) {
+  const Lz4fBlockColOff o = lz4f_block_col_off(nb);
   BlockCols c;
-  c.in_off = reinterpret_cast<u64*>(w);
-  c.out_off = c.in_off + nb;
-  c.src_off = c.out_off + nb;
-  c.in_len = reinterpret_cast<u32*>(c.src_off + nb);
-  c.out_cap = c.in_len + nb;
-  c.out_len = c.out_cap + nb;
-  c.status = reinterpret_cast<i32*>(c.out_len + nb);
-  c.src_len = reinterpret_cast<u32*>(c.status + nb);
-  c.flags = c.src_len + nb;
+  c.in_off = reinterpret_cast<u64*>(w + o.in_off);
+  c.out_off = reinterpret_cast<u64*>(w + o.out_off);
+  c.src_off = reinterpret_cast<u64*>(w + o.src_off);
+  c.in_len = reinterpret_cast<u32*>(w + o.in_len);
+  c.out_cap = reinterpret_cast<u32*>(w + o.out_cap);
+  c.out_len = reinterpret_cast<u32*>(w + o.out_len);
+  c.status = reinterpret_cast<i32*>(w + o.status);
+  c.src_len = reinterpret_cast<u32*>(w + o.src_len);
+  c.flags = reinterpret_cast<u32*>(w + o.flags);
   return c;
 }
 
-// A workspace for `total` input bytes: header | message columns | block
-// columns | [compress: a 64-byte slot per entry] | the block codec's workspace
-// | staging.
-struct Plan {
-  u32 nb_cap;
-  u64 stage_cap;
-  u64 off_msg, off_blk, off_dummy, off_inner, inner_bytes, off_stage, total;
-};
-constexpr u64 kMaxBlocks = 1ull << 30;
-
-bool enc_plan(u32 n_msgs, u64 total, u32 id, Plan* p) {
-  const u64 bs = lz4f::block_bytes(id);
-  const u64 nb = (u64)n_msgs + total / bs;
-  if (nb > kMaxBlocks) return false;
-  p->nb_cap = (u32)nb;
-  p->stage_cap = total + total / 255 + nb * (enc_slot(0) + 16);
-  p->off_msg = kHead;
-  p->off_blk = p->off_msg + 4 * list_bytes(n_msgs);
-  p->off_dummy = p->off_blk + block_cols_bytes(nb);
-  p->off_inner = p->off_dummy + round_up(64 * nb, 256);
-  p->inner_bytes = lz4_compress_workspace_bytes((u32)nb);
-  p->off_stage = round_up(p->off_inner + p->inner_bytes, 256);
-  p->total = p->off_stage + round_up(p->stage_cap, 256);
-  return true;
-}
-
-// a full compressed block of the smallest size, 64 KiB, has at least 257
-// bytes (a length byte adds at most 255), so a frame the fast route takes has
-// at most one block per 256 input bytes and one more
-bool dec_plan(u32 n_msgs, u64 total, Plan* p) {
-  const u64 nb = (u64)n_msgs + total / 256;
-  if (nb > kMaxBlocks) return false;
-  p->nb_cap = (u32)nb;
-  p->stage_cap = total + 32 * nb;
-  p->off_msg = kHead;
-  p->off_blk = p->off_msg + 4 * list_bytes(n_msgs);
-  p->off_dummy = p->off_blk + block_cols_bytes(nb);
-  p->off_inner = p->off_dummy;
-  // the block decoder's workspace: its columns for every entry, and a bitmap
-  // for `total` block bytes with 16 bytes of rounding for a block per message
-  // and per 4 KiB (64 KiB blocks that shrank 16 times).  Blocks past that go
-  // to the block decoder's one-pass kernel: slower, the same bytes.
-  p->inner_bytes = lz4_decode_workspace_bytes((u32)nb, 0) - 16 * nb + 16 * ((u64)n_msgs + total / 4096) +
-                   4 * (total / 32);
-  p->off_stage = round_up(p->off_inner + p->inner_bytes, 256);
-  p->total = p->off_stage + round_up(p->stage_cap, 256);
-  return true;
-}
-
-// the largest `total` whose workspace fits ws_bytes (the calls get no input
-// size: the workspace says what it was sized for); false below total = 0
-template <typename F>
-bool plan_for(size_t ws_bytes, Plan* p, F make) {
-  if (!make(0, p) || p->total > ws_bytes) return false;
-  u64 lo = 0, hi = 1ull << 46;  // make(lo) fits
-  while (lo + 1 < hi) {
-    const u64 mid = lo + (hi - lo) / 2;
-    Plan q;
-    if (make(mid, &q) && q.total <= ws_bytes) lo = mid;
-    else hi = mid;
-  }
-  return make(lo, p);
-}
-
 }  // namespace
-
-size_t lz4f_compress_workspace_bytes(u32 n_msgs, u64 total_in_bytes, u32 id) {
-  Plan p;
-  return enc_plan(n_msgs, total_in_bytes, id, &p) ? (size_t)p.total : 0;
-}
-size_t lz4f_decompress_workspace_bytes(u32 n_msgs, u64 total_in_bytes) {
-  Plan p;
-  return dec_plan(n_msgs, total_in_bytes, &p) ? (size_t)p.total : 0;
-}
-u32 lz4f_compress_block_capacity(u32 n_msgs, size_t ws_bytes, u32 id) {
-  Plan p;
-  return plan_for(ws_bytes, &p, [&](u64 t, Plan* q) { return enc_plan(n_msgs, t, id, q); }) ? p.nb_cap : 0;
-}
-u32 lz4f_decompress_block_capacity(u32 n_msgs, size_t ws_bytes) {
-  Plan p;
-  return plan_for(ws_bytes, &p, [&](u64 t, Plan* q) { return dec_plan(n_msgs, t, q); }) ? p.nb_cap : 0;
-}
 
 void lz4f_encode_header_counts(const void* header, Lz4fEncodeHeaderCounts* c) {
   u32 ctr[8];
@@ -973,29 +883,28 @@ void lz4f_decode_header_counts(const void* header, Lz4fDecodeHeaderCounts* c) {
   c->inner_fallback = ctr[kFdInner];
 }
 
+// every size and decision from lz4f_encode_plan (lz4_frame_plan.h)
 hipError_t launch_lz4f_encode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, u32* out_len, i32* status, u32 id, u32 flags, void* ws,
-                              size_t ws_bytes, u64 wave_min, hipStream_t stream) {
+                              hipStream_t stream, const Lz4fEncodePlan& plan) {
   if (n_msgs == 0) return hipSuccess;
-  Plan p;
-  if (id < lz4f::kMinBlockId || id > lz4f::kMaxBlockId ||
-      !plan_for(ws_bytes, &p, [&](u64 t, Plan* q) { return enc_plan(n_msgs, t, id, q); }))
-    return hipErrorInvalidValue;
+  if (!plan.valid) return hipErrorInvalidValue;
+  const Lz4fLayout& p = plan.w;
   u8* const w = static_cast<u8*>(ws);
   u32* const hdr = reinterpret_cast<u32*>(w);
   const MsgCols mc = msg_cols(w + p.off_msg, n_msgs);
   const BlockCols c = block_cols(w + p.off_blk, p.nb_cap);
   const u32 bs = lz4f::block_bytes(id);
-  hipError_t e = hipMemsetAsync(w, 0, kHead, stream);
+  hipError_t e = hipMemsetAsync(w, 0, kLz4fHead, stream);
   if (e != hipSuccess) return e;
-  lz4f_prefill_kernel<<<(p.nb_cap + 255) / 256, 256, 0, stream>>>(c, p.nb_cap, p.off_dummy);
+  lz4f_prefill_kernel<<<plan.prefill_grid, 256, 0, stream>>>(c, p.nb_cap, p.off_dummy);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  lz4f_plan_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in_off, in_len, n_msgs, bs, hdr, mc, c, p.nb_cap,
-                                                         p.off_stage, p.stage_cap);
+  lz4f_plan_kernel<<<plan.plan_grid, 64, 0, stream>>>(in_off, in_len, n_msgs, bs, hdr, mc, c, p.nb_cap, p.off_stage,
+                                                     p.stage_cap);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   // the block encoders on the block columns, with their own routing
-  e = launch_lz4_encode(in, c.in_off, c.in_len, p.nb_cap, w, c.out_off, c.out_len, c.status, w + p.off_inner,
-                        p.inner_bytes, wave_min, stream);
+  e = launch_lz4_encode(in, c.in_off, c.in_len, p.nb_cap, w, c.out_off, c.out_len, c.status, w + p.off_inner, stream,
+                        plan.inner);
   if (e != hipSuccess) return e;
   // the checksum kernel: the messages, and the entries' bytes as stored
   if (flags & lz4f::kOptContentSum) {
@@ -1004,8 +913,8 @@ hipError_t launch_lz4f_encode(const u8* in, const u64* in_off, const u32* in_len
   if (flags & lz4f::kOptBlockSums) {
     if ((e = launch_xxh_quads(StoredUnits{in, w, c}, p.nb_cap, stream)) != hipSuccess) return e;
   }
-  lz4f_assemble_kernel<<<n_msgs, 64, 0, stream>>>(in, in_len, out, out_off, out_len, status, id, flags, hdr, mc, c,
-                                                  w);
+  lz4f_assemble_kernel<<<plan.assemble_grid, 64, 0, stream>>>(in, in_len, out, out_off, out_len, status, id, flags, hdr,
+                                                             mc, c, w);
   return hipGetLastError();
 }
 
@@ -1023,59 +932,42 @@ hipError_t launch_lz4f_content_sizes(const u8* in, const u64* in_off, const u32*
 
 namespace {
 // the length pass on the claimed entries: lanes, then the listed large blocks
-// (a grid of 256 blocks: with none listed each wave reads the count and leaves)
-hipError_t launch_length_pass(const u8* in, u32* hdr, const BlockCols& c, u32 nb_cap, u32 wave_min,
+hipError_t launch_length_pass(const u8* in, u32* hdr, const BlockCols& c, const Lz4fDecodePlan& plan,
                               hipStream_t stream) {
-  const u32 grid = (nb_cap + 63) / 64 < 4096 ? (nb_cap + 63) / 64 : 4096;
-  lz4f_length_lane_kernel<<<grid, 64, 0, stream>>>(in, hdr, c, nb_cap, wave_min);
+  lz4f_length_lane_kernel<<<plan.length_lane_grid, 64, 0, stream>>>(in, hdr, c, plan.w.nb_cap, plan.length_wave_min);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  lz4f_length_wave_kernel<<<256, kLenWaves * 64, 0, stream>>>(in, hdr, c);
+  lz4f_length_wave_kernel<<<plan.length_wave_grid, kLenWaves * 64, 0, stream>>>(in, hdr, c);
   return hipGetLastError();
 }
 }  // namespace
 
-// The wave threshold of the length pass from option lz4f_length_wave_min.
-// Automatic: 2 KiB whatever the batch.  Measured on MI355X (DESIGN.md section
-// 5, "LZ4 frames without a content size", the lane-against-wave table): the
-// wave won at every point, from 1.14x (4,096 blocks of 4 KiB, 2.7 KB stored)
-// to 10.7x (64 blocks of 4 MiB); the smallest stored size in the table is
-// 2.7 KB and nothing below it was measured, so blocks of at most 2 KiB stay
-// with the lanes.  (The first build took the block decoder's rule, 2 KiB up
-// to 256 block entries and 64 KiB above; the table did not bear out the 64
-// KiB.)
-u32 lz4f_length_wave_min(i64 option) {
-  if (option < 0) return 2048u;
-  return option >= 0xFFFFFFFFll ? 0xFFFFFFFFu : (u32)option;
-}
-
+// every size and decision of the two launches below from lz4f_decode_plan (lz4_frame_plan.h)
 hipError_t launch_lz4f_decoded_lengths(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* lengths,
-                                       i32* status, void* ws, size_t ws_bytes, u32 length_wave_min,
-                                       hipStream_t stream) {
+                                       i32* status, void* ws, hipStream_t stream, const Lz4fDecodePlan& plan) {
   if (n_msgs == 0) return hipSuccess;
-  Plan p;
-  if (!plan_for(ws_bytes, &p, [&](u64 t, Plan* q) { return dec_plan(n_msgs, t, q); })) return hipErrorInvalidValue;
+  if (!plan.valid) return hipErrorInvalidValue;
+  const Lz4fLayout& p = plan.w;
   u8* const w = static_cast<u8*>(ws);
   u32* const hdr = reinterpret_cast<u32*>(w);
   const MsgCols mc = msg_cols(w + p.off_msg, n_msgs);
   const BlockCols c = block_cols(w + p.off_blk, p.nb_cap);
   hipError_t e = hipMemsetAsync(w, 0, p.off_dummy, stream);
   if (e != hipSuccess) return e;
-  lz4f_length_index_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, lengths, status, hdr, mc,
-                                                                 c, p.nb_cap);
+  lz4f_length_index_kernel<<<plan.msg_grid, 64, 0, stream>>>(in, in_off, in_len, n_msgs, lengths, status, hdr, mc, c,
+                                                            p.nb_cap);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  if ((e = launch_length_pass(in, hdr, c, p.nb_cap, length_wave_min, stream)) != hipSuccess) return e;
-  lz4f_place_kernel<<<(n_msgs + 3) / 4, 256, 0, stream>>>(n_msgs, nullptr, nullptr, mc, c, lengths, status);
+  if ((e = launch_length_pass(in, hdr, c, plan, stream)) != hipSuccess) return e;
+  lz4f_place_kernel<<<plan.place_grid, 256, 0, stream>>>(n_msgs, nullptr, nullptr, mc, c, lengths, status);
   return hipGetLastError();
 }
 
 hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
                               const u64* out_off, const u32* out_cap, u32* out_len, i32* status, void* ws,
-                              size_t ws_bytes, bool force_serial, bool nosize_fast, bool linked_fast,
-                              u32 length_wave_min, hipStream_t stream) {
+                              hipStream_t stream, const Lz4fDecodePlan& plan) {
   if (n_msgs == 0) return hipSuccess;
-  Plan p;
-  if (!plan_for(ws_bytes, &p, [&](u64 t, Plan* q) { return dec_plan(n_msgs, t, q); })) return hipErrorInvalidValue;
+  if (!plan.valid) return hipErrorInvalidValue;
+  const Lz4fLayout& p = plan.w;
   u8* const w = static_cast<u8*>(ws);
   u32* const hdr = reinterpret_cast<u32*>(w);
   const MsgCols mc = msg_cols(w + p.off_msg, n_msgs);
@@ -1084,40 +976,39 @@ hipError_t launch_lz4f_decode(const u8* in, const u64* in_off, const u32* in_len
   // body, which the block decoder answers without touching the output
   hipError_t e = hipMemsetAsync(w, 0, p.off_dummy, stream);
   if (e != hipSuccess) return e;
-  lz4f_index_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out_off, out_cap, out_len,
-                                                          status, hdr, mc, c, p.nb_cap, p.off_stage, p.stage_cap,
-                                                          force_serial ? 1u : 0u, nosize_fast ? 1u : 0u,
-                                                          linked_fast ? 1u : 0u);
+  lz4f_index_kernel<<<plan.msg_grid, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out_off, out_cap, out_len, status, hdr,
+                                                     mc, c, p.nb_cap, p.off_stage, p.stage_cap,
+                                                     plan.force_serial ? 1u : 0u, plan.nosize_fast ? 1u : 0u,
+                                                     plan.linked_fast ? 1u : 0u);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const u32* inner_fallback = nullptr;
-  if (!force_serial && nosize_fast) {
-    if ((e = launch_length_pass(in, hdr, c, p.nb_cap, length_wave_min, stream)) != hipSuccess) return e;
-    lz4f_place_kernel<<<(n_msgs + 3) / 4, 256, 0, stream>>>(n_msgs, out_off, out_cap, mc, c, nullptr, nullptr);
+  if (!plan.force_serial && plan.nosize_fast) {
+    if ((e = launch_length_pass(in, hdr, c, plan, stream)) != hipSuccess) return e;
+    lz4f_place_kernel<<<plan.place_grid, 256, 0, stream>>>(n_msgs, out_off, out_cap, mc, c, nullptr, nullptr);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  if (!force_serial) {
-    const u32 grid = (p.nb_cap + 3) / 4 < 8192 ? (p.nb_cap + 3) / 4 : 8192;
-    lz4f_stage_kernel<<<grid, 256, 0, stream>>>(in, out, w, c, p.nb_cap);
+  if (!plan.force_serial) {
+    lz4f_stage_kernel<<<plan.stage_grid, 256, 0, stream>>>(in, out, w, c, p.nb_cap);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // option lz4f_linked_fast: the flags column carries the prefixes, the
     // route column the chains' results; without it, the launch of before
     const Lz4Chains chains{c.flags,  kBlkPrefixShift, kBlkChained,      kBlkRaw,          n_msgs, mc.first,
                            mc.nb,    mc.route,        kRouteLinkedFast, 1u,               kRouteChainDone};
     e = launch_lz4_decode2(w, c.in_off, c.in_len, p.nb_cap, out, c.out_off, c.out_cap, c.out_len, c.status,
-                           w + p.off_inner, p.inner_bytes, stream, nullptr, linked_fast ? &chains : nullptr);
+                           w + p.off_inner, stream, nullptr, plan.inner, plan.linked_fast ? &chains : nullptr);
     if (e != hipSuccess) return e;
     // the checksum kernel: block checksums of the listed entries, then (the
     // chains' results and the blocks' places are known) the content checksums
     // of the pending frames; each leaves at once when index counted none
     if ((e = launch_xxh_quads(BlockSumUnits{in, hdr, c}, p.nb_cap, stream)) != hipSuccess) return e;
-    lz4f_verdict_kernel<<<(p.nb_cap + 63) / 64, 64, 0, stream>>>(c, p.nb_cap, hdr);
+    lz4f_verdict_kernel<<<plan.verdict_grid, 64, 0, stream>>>(c, p.nb_cap, hdr);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if ((e = launch_xxh_quads(ContentUnits{in, in_off, out, out_off, hdr, mc, c}, n_msgs, stream)) != hipSuccess)
       return e;
-    inner_fallback = reinterpret_cast<const u32*>(w + p.off_inner) + 3;  // lz4_decode2.hip: its fallback counter
+    inner_fallback = reinterpret_cast<const u32*>(w + p.off_inner) + kL4CtrFallback;  // the block decoder's counter
   }
-  lz4f_finish_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_cap, out_len,
-                                                           status, hdr, mc, c, inner_fallback);
+  lz4f_finish_kernel<<<plan.msg_grid, 64, 0, stream>>>(in, in_off, in_len, n_msgs, out, out_off, out_cap, out_len,
+                                                      status, hdr, mc, c, inner_fallback);
   return hipGetLastError();
 }
 

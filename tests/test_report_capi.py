@@ -158,6 +158,44 @@ def test_lz4_routing(lib):
     assert r.bitmap_words_capacity == 4 * 5 + 4  # the two-pass minimum: 4 words per message + 4
 
 
+def test_lz4_compress_routing(lib):
+    """Route and wave_min are the plan's (csrc/lz4_plan.h): the wave encoder up
+    to 256 bodies, the lanes alone on a workspace of the tables."""
+    r = fsg.Lz4EncodeReport()
+    zero = ctypes.create_string_buffer(256)
+    for n, wave_min in ((256, 8192), (257, 0xFFFFFFFF)):
+        ws = lib.fsg_lz4_compress_workspace_bytes(n)
+        assert ws == 256 + -(-4 * n // 256) * 256 + 16384 * n
+        assert lib.fsg_lz4_compress_report(None, n, ws, ctypes.byref(r)) == INVALID_ARG
+        assert lib.fsg_lz4_compress_report(zero, n, ws, ctypes.byref(r)) == 0
+        assert r.path == 0 and r.wave_min == wave_min and r.lane_messages == n and r.wave_messages == 0
+        assert lib.fsg_lz4_compress_report(None, n, ws - 1, ctypes.byref(r)) == 0
+        assert r.path == 1 and r.wave_min == 0xFFFFFFFF and r.lane_messages == n
+
+
+def test_lz4f_block_entries(lib):
+    """The frame reports' block_entries is the plan's capacity
+    (csrc/lz4_frame_plan.h): 0 and an invalid argument below the size for no
+    input, then an entry per message and per block the workspace was sized for."""
+    zero = ctypes.create_string_buffer(256)
+    d = fsg.Lz4fDecodeReport()
+    lo = lib.fsg_lz4f_decompress_workspace_bytes(1, 0)
+    assert lo == 3072
+    assert lib.fsg_lz4f_decompress_report(zero, 1, lo - 1, ctypes.byref(d)) == INVALID_ARG and d.block_entries == 0
+    assert lib.fsg_lz4f_decompress_report(None, 1, lo, ctypes.byref(d)) == INVALID_ARG
+    assert lib.fsg_lz4f_decompress_report(zero, 1, lo, ctypes.byref(d)) == 0 and d.block_entries == 1
+    ws = lib.fsg_lz4f_decompress_workspace_bytes(1, 1 << 20)
+    assert lib.fsg_lz4f_decompress_report(zero, 1, ws, ctypes.byref(d)) == 0 and d.block_entries == 1 + (1 << 20) // 256
+    e = fsg.Lz4fEncodeReport()
+    for n, total, entries, wave_min in ((1, 255 << 16, 256, 8192), (1, 256 << 16, 257, 0xFFFFFFFF)):
+        ws = lib.fsg_lz4f_compress_workspace_bytes(n, total, 4)
+        assert lib.fsg_lz4f_compress_report(zero, n, ws, 4, ctypes.byref(e)) == 0
+        assert e.block_entries == entries and e.block_wave_min == wave_min
+    assert lib.fsg_lz4f_compress_report(zero, 1, lib.fsg_lz4f_compress_workspace_bytes(1, 0, 4) - 1, 4,
+                                        ctypes.byref(e)) == INVALID_ARG and e.block_entries == 0
+    assert lib.fsg_lz4f_compress_report(zero, 1, 1 << 20, 3, ctypes.byref(e)) == INVALID_ARG
+
+
 def test_null_out_is_invalid(lib):
     zero = ctypes.create_string_buffer(256)
     assert lib.fsg_decompress_report(zero, 7, 0, 0, None) == INVALID_ARG
