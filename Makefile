@@ -6,7 +6,7 @@ PKG      := flare-cpp_amd
 LIB      := $(PKG)/lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall
 CSRC     := $(PKG)/csrc/capi.hip $(PKG)/csrc/snappy_decode.hip $(PKG)/csrc/snappy_decode_v3.hip $(PKG)/csrc/snappy_decode_v4.hip $(PKG)/csrc/snappy_decode_partial.hip \
-            $(PKG)/csrc/snappy_encode.hip $(PKG)/csrc/snappy_encode_v3.hip $(PKG)/csrc/snappy_encode_wave.hip $(PKG)/csrc/gather.hip $(PKG)/csrc/pack.hip $(PKG)/csrc/lz4.hip $(PKG)/csrc/lz4_decode2.hip $(PKG)/csrc/lz4_encode_wave.hip $(PKG)/csrc/lz4_frame.hip $(PKG)/csrc/inflate.hip $(PKG)/csrc/inflate_units.hip $(PKG)/csrc/deflate.hip $(PKG)/csrc/deflate_level.hip
+            $(PKG)/csrc/snappy_encode.hip $(PKG)/csrc/snappy_encode_v3.hip $(PKG)/csrc/snappy_encode_wave.hip $(PKG)/csrc/gather.hip $(PKG)/csrc/pack.hip $(PKG)/csrc/lz4.hip $(PKG)/csrc/lz4_decode2.hip $(PKG)/csrc/lz4_encode_wave.hip $(PKG)/csrc/lz4_frame_encode.hip $(PKG)/csrc/lz4_frame_decode.hip $(PKG)/csrc/inflate.hip $(PKG)/csrc/inflate_units.hip $(PKG)/csrc/deflate.hip $(PKG)/csrc/deflate_level.hip
 CHDRS    := $(wildcard $(PKG)/csrc/*.h) include/flare_snappy_gpu.h include/flare_lz4_gpu.h include/flare_deflate_gpu.h include/flare_deflate_compress_gpu.h include/flare_deflate_level_gpu.h include/flare_deflate_index_gpu.h
 OBJDIR   := build/obj
 

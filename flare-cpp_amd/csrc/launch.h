@@ -90,7 +90,8 @@ hipError_t launch_lz4_decode2(const u8* in, const u64* in_off, const u32* in_len
                               hipStream_t stream, hipStream_t pass1_stream, const Lz4DecodePlan& p,
                               const Lz4Chains* chains = nullptr);
 
-// ---- LZ4 frames (lz4_frame.hip; include/flare_lz4_gpu.h, "LZ4 frames").  The
+// ---- LZ4 frames (lz4_frame_encode.hip, lz4_frame_decode.hip;
+// include/flare_lz4_gpu.h, "LZ4 frames").  The
 // calls get no input size: the workspace says what it was sized for, and the
 // plan's w.nb_cap gives the block entries it holds (lz4_frame_plan.h:
 // lz4f_*_workspace_bytes, lz4f_encode_plan and lz4f_decode_plan, inline).

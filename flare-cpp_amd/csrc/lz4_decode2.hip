@@ -42,7 +42,8 @@
 // Messages whose bitmap does not fit the workspace get kNeedFallback and are
 // decoded by lz4.hip's lane-per-message kernel.
 //
-// Linked LZ4 frame blocks (launch.h, Lz4Chains; lz4_frame.hip): a message may
+// Linked LZ4 frame blocks (launch.h, Lz4Chains; lz4_frame_decode.hip): a
+// message may
 // begin with a prefix, bytes of history directly below its slot.  The kernels
 // are templates on that; without chains the launch takes the forms without a
 // prefix, whose instructions are those of the kernels before the templates.

@@ -1,23 +1,14 @@
-// lz4_frame.hip -- LZ4 frame bodies (LZ4 Frame Format 1.6.x, what
-// LZ4F_compressFrame and the lz4 command write) on the batch layout of the
-// block codec: include/flare_lz4_gpu.h, "LZ4 frames".
+// lz4_frame_decode.hip -- LZ4 frame bodies (LZ4 Frame Format 1.6.x) on the
+// batch layout of the block codec, the decompress side and the lengths call:
+// include/flare_lz4_gpu.h, "LZ4 frames".
 //
-// A frame with independent blocks is a list of small LZ4 blocks, so the block
-// codecs this library already has (lz4.hip, lz4_encode_wave.hip,
-// lz4_decode2.hip) run a frame's blocks as if they were messages; the kernels
-// here only cut messages into blocks and put frames together (compress), or
-// take frames apart and judge the result (decompress).  Those launches are
-// called as they are, on the plans the frame's plan holds for them;
-// launch_lz4_decode2 alone takes one more argument, for the linked frames
-// below.  Workspace layouts, capacities, thresholds and grid sizes:
-// lz4_frame_plan.h (tests/cpp/test_lz4_plan.cc).
+// The block decoder this library already has (lz4_decode2.hip) runs a frame's
+// blocks as if they were messages, on the plan the frame's plan holds for it
+// and with one more argument for the linked frames below; the kernels here
+// only take frames apart and judge the result.  Workspace layout, capacities,
+// thresholds and grid sizes: lz4_frame_plan.h.  A frame's structure is read by
+// the one walk of lz4_frame_format.h (tests/cpp/test_lz4f_walk.cc).
 //
-// Compress: plan (a lane per message: its blocks' columns, staging slots from
-// two counters) -> launch_lz4_encode on the block columns -> XXH32 of the
-// inputs when a content checksum is asked for, and of every block's bytes as
-// stored when block checksums are (the checksum kernel, lz4f_xxh.h: a quad of
-// lanes per unit) -> assemble (a wave per message: prefix sum of the stored
-// sizes, size words, block copies, block checksums, descriptor, end mark).
 // Decompress: index (a lane per message: descriptor, route, the walk over the
 // block size words, block columns) -> stage (a wave per block: varint32 +
 // block bytes into the workspace, a raw block straight to its place) ->
@@ -41,23 +32,16 @@
 // in order (lz4_decode2.hip, lz4_exec_chain_kernel).  Finish accepts such a
 // frame only when its chain ran to the end.
 #include "launch.h"
+#include "lz4_frame_cols.h"
 #include "lz4_frame_format.h"
 #include "lz4_frame_length.h"
 #include "lz4f_xxh.h"
-#include "snappy_device.h"
 
 namespace fsg {
 
 namespace {
 
 // ---- workspace header (the first 256 bytes; u32 indices)
-// compress
-constexpr u32 kFcBlocks = 0;    // blocks asked for (past the capacity when a message did not fit)
-constexpr u32 kFcRaw = 1;       // blocks stored raw
-constexpr u32 kFcOverflow = 2;  // messages whose blocks did not fit the workspace
-constexpr u32 kFcListed = 3;    // blocks of the messages that fitted
-constexpr u32 kFcStage = 4;     // u64: staging bytes asked for
-// decompress
 constexpr u32 kFdBlocks = 0;    // block entries asked for
 constexpr u32 kFdFastMsgs = 1, kFdFastBlocks = 2, kFdEmpty = 3;
 constexpr u32 kFdLinked = 4, kFdNoSize = 5, kFdRejected = 6, kFdForced = 7;
@@ -88,201 +72,7 @@ constexpr u32 kBlkMaxShift = 8;  // with kBlkUnknown: log2 of the frame's block 
 // once the length pass, which reads f >> kBlkMaxShift, is over)
 constexpr u32 kBlkPrefixShift = 16;
 
-constexpr u32 kNoFit = 0xFFFFFFFFu;
-
-// (the staging slots of a block, enc_slot and dec_slot: lz4_frame_plan.h)
-
-__device__ __forceinline__ u32 wave_scan(u32 v) { return wave_incl_scan(v); }
-
-// adds `pred` lanes to a counter: one atomic for the wave's active lanes
-__device__ __forceinline__ void count_lanes(u32* ctr, bool pred) {
-  const u64 b = __ballot(pred);
-  const u64 act = __ballot(true);
-  if (b && __lane_id() == (u32)__builtin_ctzll(act)) atomicAdd(ctr, (u32)__builtin_popcountll(b));
-}
-
-// n bytes from s to d by one wave, exactly: single bytes up to d's 16-byte
-// boundary, 16 bytes per lane, single bytes at the end
-__device__ __forceinline__ void wave_copy(u8* d, const u8* s, u32 n, u32 lane) {
-  u32 head = (16u - (u32)(reinterpret_cast<uintptr_t>(d) & 15)) & 15;
-  if (head > n) head = n;
-  if (lane < head) d[lane] = s[lane];
-  const u32 body = (n - head) & ~15u;
-  for (u32 i = 16 * lane; i < body; i += 1024) copy16(d + head + i, s + head + i);
-  const u32 done = head + body;
-  if (done + lane < n) d[done + lane] = s[done + lane];
-}
-
-struct BlockCols {
-  u64* in_off;   // compress: into d_in; decompress: staged body, into the workspace
-  u64* out_off;  // compress: staging slot, into the workspace; decompress: into d_out
-  u64* src_off;  // decompress: the stored block's bytes, into d_in
-  u32* in_len;
-  u32* out_cap;
-  u32* out_len;
-  i32* status;
-  u32* src_len;  // decompress: stored size
-  u32* flags;
-};
-
-struct MsgCols {
-  u32* route;
-  u32* first;
-  u32* nb;
-  u32* xxh;
-};
-
-// ================================================================ compress
-
-// every block entry: an empty input and a 64-byte slot of its own, so that
-// the entries past the batch's blocks encode to nothing anybody reads
-__global__ __launch_bounds__(256) void lz4f_prefill_kernel(BlockCols c, u32 nb_cap, u64 dummy_off) {
-  const u32 e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= nb_cap) return;
-  c.in_off[e] = 0;
-  c.in_len[e] = 0;
-  c.out_off[e] = dummy_off + 64ull * e;
-}
-
-__global__ __launch_bounds__(64) void lz4f_plan_kernel(const u64* __restrict__ in_off, const u32* __restrict__ in_len,
-                                                     u32 n_msgs, u32 bs, u32* hdr, MsgCols mc, BlockCols c, u32 nb_cap,
-                                                     u64 stage_off, u64 stage_cap) {
-  const u32 m = blockIdx.x * 64 + threadIdx.x;
-  if (m >= n_msgs) return;
-  const u32 n = in_len[m];
-  const u32 nb = (u32)(((u64)n + bs - 1) / bs);
-  mc.nb[m] = nb;
-  mc.first[m] = 0;
-  if (nb == 0) return;
-  const u32 last = n - (nb - 1) * bs;
-  const u64 need = (u64)(nb - 1) * enc_slot(bs) + enc_slot(last);
-  const u32 base = atomicAdd(&hdr[kFcBlocks], nb);
-  u64 sb = atomicAdd(reinterpret_cast<unsigned long long*>(hdr + kFcStage), (unsigned long long)need);
-  if ((u64)base + nb > nb_cap || sb + need > stage_cap) {
-    mc.first[m] = kNoFit;
-    atomicAdd(&hdr[kFcOverflow], 1u);
-    return;
-  }
-  mc.first[m] = base;
-  atomicAdd(&hdr[kFcListed], nb);
-  const u64 io = in_off[m];
-  for (u32 k = 0; k < nb; ++k) {
-    const u32 L = k + 1 < nb ? bs : last;
-    c.in_off[base + k] = io + (u64)k * bs;
-    c.in_len[base + k] = L;
-    c.out_off[base + k] = stage_off + sb;
-    sb += enc_slot(L);
-  }
-}
-
-// ---- units of the checksum kernel (lz4f_xxh.h)
-// each body of a batch: the content checksum of compress, fsg_lz4f_xxh32_batch
-struct BodyUnits {
-  const u8* in;
-  const u64* in_off;
-  const u32* in_len;
-  u32 seed;
-  u32* xxh;
-  __device__ bool any() const { return true; }
-  __device__ bool get(u32 m, const u8** p, u64* n, u32* sd) const {
-    *p = in + in_off[m];
-    *n = in_len[m];
-    *sd = seed;
-    return true;
-  }
-  __device__ void put(u32 m, u32 h) const { xxh[m] = h; }
-};
-
-// compress, block checksums: every block entry that holds a block (the
-// prefilled rest is empty), over the bytes as stored -- the choice of
-// lz4f_assemble_kernel; the word goes to src_len, idle on this side
-struct StoredUnits {
-  const u8* in;
-  const u8* ws;
-  BlockCols c;
-  __device__ bool any() const { return true; }
-  __device__ bool get(u32 e, const u8** p, u64* n, u32* sd) const {
-    const u32 L = c.in_len[e];
-    if (L == 0) return false;
-    const u32 hl = (u32)varint32_len(L);
-    const u32 csize = c.out_len[e] - hl;
-    const bool raw = csize >= L;
-    *p = raw ? in + c.in_off[e] : ws + c.out_off[e] + hl;
-    *n = raw ? L : csize;
-    *sd = 0;
-    return true;
-  }
-  __device__ void put(u32 e, u32 h) const { c.src_len[e] = h; }
-};
-
-// One wave per message: the frame from the staged blocks.
-__global__ __launch_bounds__(64) void lz4f_assemble_kernel(const u8* __restrict__ in, const u32* __restrict__ in_len,
-                                                         u8* out, const u64* __restrict__ out_off,
-                                                         u32* __restrict__ out_len, i32* __restrict__ status, u32 id,
-                                                         u32 flags, u32* hdr, MsgCols mc, BlockCols c,
-                                                         const u8* ws) {
-  const u32 m = blockIdx.x;
-  const u32 lane = threadIdx.x;
-  const u32 n = in_len[m];
-  const u32 first = mc.first[m], nb = mc.nb[m];
-  if (first == kNoFit || lz4f::max_frame_length(n, id, flags) > 0xFFFFFFFFull) {
-    if (lane == 0) {
-      out_len[m] = 0;
-      status[m] = kCorrupt;
-    }
-    return;
-  }
-  u8* const ob = out + out_off[m];
-  if (lane == 0) lz4f::write_header(ob, n, id, flags);
-  const u32 bsum = (flags & lz4f::kOptBlockSums) ? 4 : 0;
-  u64 pos = n && !(flags & lz4f::kOptNoSize) ? 15 : 7;
-  u32 raws = 0;
-  for (u32 k0 = 0; k0 < nb; k0 += 64) {
-    const u32 k = k0 + lane;
-    const bool valid = k < nb;
-    u32 L = 0, stored = 0, hl = 0;
-    bool raw = false;
-    u64 src = 0;
-    if (valid) {
-      const u32 e = first + k;
-      L = c.in_len[e];
-      hl = (u32)varint32_len(L);
-      const u32 csize = c.out_len[e] - hl;
-      raw = csize >= L;
-      stored = raw ? L : csize;
-      src = raw ? c.in_off[e] : c.out_off[e] + hl;
-    }
-    const u32 sz = valid ? 4 + stored + bsum : 0;
-    const u32 incl = wave_scan(sz);
-    const u64 at = pos + (incl - sz);
-    if (valid) {
-      lz4f::wr32(ob + at, raw ? (L | lz4f::kRawBit) : stored);
-      if (bsum) lz4f::wr32(ob + at + 4 + stored, c.src_len[first + k]);
-    }
-    raws += (u32)__builtin_popcountll(__ballot(valid && raw));
-    const u32 cnt = nb - k0 < 64 ? nb - k0 : 64;
-    for (u32 j = 0; j < cnt; ++j) {
-      const u64 s = __shfl(src, j, 64), a = __shfl(at, j, 64);
-      const u32 len = __shfl(stored, j, 64);
-      const bool r = __shfl((int)raw, j, 64);
-      wave_copy(ob + a + 4, (r ? in : ws) + s, len, lane);
-    }
-    pos += __shfl(incl, 63, 64);
-  }
-  if (lane == 0) {
-    lz4f::wr32(ob + pos, 0);
-    pos += 4;
-    if (flags & lz4f::kOptContentSum) {
-      lz4f::wr32(ob + pos, mc.xxh[m]);
-      pos += 4;
-    }
-    out_len[m] = (u32)pos;
-    status[m] = kOk;
-    if (raws) atomicAdd(&hdr[kFcRaw], raws);
-  }
-}
-
-// ================================================================ decompress
+// (the staging slot of a block, dec_slot: lz4_frame_plan.h)
 
 __global__ __launch_bounds__(64) void lz4f_sizes_kernel(const u8* __restrict__ in, const u64* __restrict__ in_off,
                                                       const u32* __restrict__ in_len, u32 n_msgs, u64* sizes,
@@ -295,72 +85,63 @@ __global__ __launch_bounds__(64) void lz4f_sizes_kernel(const u8* __restrict__ i
   status[m] = st;
 }
 
-// The block structure of a frame without a content size, from the size words
-// alone: every size at most the block maximum (and not 0, unless zero_raw
-// allows an empty raw block, which the serial decoder accepts) and inside the
-// input with its block checksum, the end mark, the content checksum when
-// flagged, nothing after the frame.  *nb blocks, *need staging bytes for the
-// compressed ones, *xxh the stated content checksum.
-__device__ inline bool walk_blocks(const u8* ib, u64 n, const lz4f::Header& h, bool zero_raw, u32* nb, u64* need,
-                                   u32* xxh) {
-  const u32 bsum = (h.flg & lz4f::kFlgBlockSum) ? 4 : 0;
-  u64 ip = h.len, nd = 0;
-  u32 k = 0;
-  for (;; ++k) {
-    if (n - ip < 4) return false;
-    const u32 word = lz4f::rd32(ib + ip);
-    ip += 4;
-    if (word == 0) break;
-    const u32 sz = word & ~lz4f::kRawBit;
-    if ((sz == 0 && !zero_raw) || sz > h.block_max || n - ip < (u64)sz + bsum) return false;
-    if (!(word & lz4f::kRawBit)) {
-      if (sz == 0) return false;  // a compressed block has a token
-      nd += dec_slot(sz);
-    }
-    ip += sz + bsum;
-  }
-  *xxh = 0;
-  if (h.flg & lz4f::kFlgSum) {
-    if (n - ip < 4) return false;
-    *xxh = lz4f::rd32(ib + ip);
-    ip += 4;
-  }
-  if (ip != n) return false;
-  *nb = k;
-  *need = nd;
+// The claim of a frame check_blocks accepted: nb entries from *base and, with
+// `stage`, `need` staging bytes from *sb and the counts the checksum kernels
+// leave by.  false: no room in the workspace; else the message's columns.
+__device__ inline bool claim_blocks(u32* hdr, MsgCols mc, u32 m, const lz4f::Header& h, u32 nb, u32 xxh, u32 route,
+                                    u32 nb_cap, bool stage, u64 need, u64 stage_cap, u32* base, u64* sb) {
+  *base = atomicAdd(&hdr[kFdBlocks], nb);
+  *sb = stage ? atomicAdd(reinterpret_cast<unsigned long long*>(hdr + kFdStage), (unsigned long long)need) : 0;
+  if ((u64)*base + nb > nb_cap || (stage && *sb + need > stage_cap)) return false;
+  if (stage && (h.flg & lz4f::kFlgBlockSum)) atomicAdd(&hdr[kFdSumBlocks], nb);
+  if (stage && (h.flg & lz4f::kFlgSum)) atomicAdd(&hdr[kFdSumMsgs], 1u);
+  mc.xxh[m] = xxh;
+  mc.first[m] = *base;
+  mc.nb[m] = nb;
+  mc.route[m] = route;
   return true;
 }
 
-// The entries [base, base + nb) of a frame walk_blocks accepted: where the
-// stored bytes are, the flags with "length unknown", a staging slot from `at`
-// on for a compressed block (at = 0: none, the lengths call).  in_len,
-// out_off and out_cap stay 0 -- an empty body for the block decoder -- until
-// the place kernel knows the lengths.
-__device__ inline void list_unknown(const u8* ib, const lz4f::Header& h, u64 io, u32 nb, u32 base, u64 at,
-                                    BlockCols c, u32 more_flags = 0) {
-  const u32 bsum = (h.flg & lz4f::kFlgBlockSum) ? 4 : 0;
-  const u32 common = kBlkListed | kBlkUnknown | more_flags | (bsum ? kBlkSum : 0) |
-                     ((u32)(31 - __builtin_clz(h.block_max)) << kBlkMaxShift);
-  u64 ip = h.len;
+// The listing pass over the nb blocks check_blocks accepted (nothing is tested
+// again), entries from `base` on: where the stored bytes are, the flags, a
+// staging slot from `at` on for a compressed block (at = 0: none, the lengths
+// call).  A sized frame's entries get places and lengths, a chained one its
+// prefix.  Without a content size the flags say "length unknown" with the
+// block maximum; in_len, out_off and out_cap stay 0 -- an empty body for the
+// block decoder -- until the place kernel knows the lengths.
+__device__ inline void list_blocks(const u8* ib, u64 n, const lz4f::Header& h, u64 io, u64 oo, u32 nb, u32 base,
+                                   u64 at, bool chain, BlockCols c) {
+  const bool sized = h.size != lz4f::kNoSize;
+  const u64 bs = h.block_max;
+  const u32 common = kBlkListed | ((h.flg & lz4f::kFlgBlockSum) ? kBlkSum : 0) | (chain ? kBlkChained : 0) |
+                     (sized ? 0 : kBlkUnknown | ((u32)(31 - __builtin_clz(h.block_max)) << kBlkMaxShift));
+  lz4f::BlockWalk w = lz4f::begin_blocks(ib, n, h);
+  lz4f::Block b, next;
+  lz4f::next_block<false>(&w, &next);
   for (u32 k = 0; k < nb; ++k) {
+    b = next;  // (the next word loads under this block's stores; after the last block it is the end mark, dropped)
+    lz4f::next_block<false>(&w, &next);
     const u32 e = base + k;
-    const u32 word = lz4f::rd32(ib + ip);
-    const u32 sz = word & ~lz4f::kRawBit;
-    const bool raw = word & lz4f::kRawBit;
-    ip += 4;
-    c.src_off[e] = io + ip;
-    c.src_len[e] = sz;
-    c.flags[e] = common | (raw ? kBlkRaw : 0);
-    if (!raw && at) {
-      c.in_off[e] = at;
-      at += dec_slot(sz);
+    const u32 exp = sized ? (u32)(h.size - k * bs < bs ? h.size - k * bs : bs) : 0;
+    u32 f = common | (b.raw ? kBlkRaw : 0);
+    c.src_off[e] = io + b.at;
+    c.src_len[e] = b.size;
+    if (sized) {
+      c.out_off[e] = oo + k * bs;
+      c.out_cap[e] = exp;
+      if (chain) f |= lz4f::linked_prefix(k * bs) << kBlkPrefixShift;
     }
-    ip += sz + bsum;
+    c.flags[e] = f;
+    if (!b.raw && at) {
+      c.in_off[e] = at;
+      if (sized) c.in_len[e] = (u32)varint32_len(exp) + b.size;
+      at += dec_slot(b.size);
+    }
   }
 }
 
-// One lane per message: descriptor, route, and for the fast route the walk
-// over the block size words (two walks: sizes, then columns).
+// One lane per message: descriptor, route, and for the fast routes the walk
+// over the block size words (two passes: validate, then list).
 __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ in, const u64* __restrict__ in_off,
                                                       const u32* __restrict__ in_len, u32 n_msgs,
                                                       const u64* __restrict__ out_off, const u32* __restrict__ out_cap,
@@ -380,14 +161,15 @@ __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ i
     return;
   }
   const u64 cap = out_cap[m];
+  const bool sized = h.size != lz4f::kNoSize;
   // linked blocks on the fast route: with a content size, or with both options
   const bool linked = !(h.flg & lz4f::kFlgIndep);
-  const bool chain = linked && linked_fast && !force_serial && (h.size != lz4f::kNoSize || nosize_fast);
-  if (chain && h.size != lz4f::kNoSize && h.size > cap) {  // (the serial decoder answers from the descriptor)
+  const bool chain = linked && linked_fast && !force_serial && (sized || nosize_fast);
+  if (chain && sized && h.size > cap) {  // (the serial decoder answers from the descriptor)
     mc.route[m] = kRouteRejected;
     return;
   }
-  if (h.size != lz4f::kNoSize && h.size > cap) {
+  if (sized && h.size > cap) {
     out_len[m] = h.size > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)h.size;
     status[m] = kSlotTooSmall;
     return;
@@ -409,86 +191,20 @@ __global__ __launch_bounds__(64) void lz4f_index_kernel(const u8* __restrict__ i
     mc.route[m] = kRouteLinked;
     return;
   }
-  if (h.size == lz4f::kNoSize) {
-    if (!nosize_fast) {
-      mc.route[m] = kRouteNoSize;
-      return;
-    }
-    // no content size: the blocks' lengths are unknown until the length pass
-    mc.route[m] = kRouteRejected;
-    u32 nb, xxh;
-    u64 need;
-    if (!walk_blocks(ib, n, h, false, &nb, &need, &xxh)) return;
-    const u32 base = atomicAdd(&hdr[kFdBlocks], nb);
-    const u64 sb = atomicAdd(reinterpret_cast<unsigned long long*>(hdr + kFdStage), (unsigned long long)need);
-    if ((u64)base + nb > nb_cap || sb + need > stage_cap) return;
-    list_unknown(ib, h, in_off[m], nb, base, stage_off + sb, c, chain ? kBlkChained : 0);
-    if (h.flg & lz4f::kFlgBlockSum) atomicAdd(&hdr[kFdSumBlocks], nb);
-    if (h.flg & lz4f::kFlgSum) atomicAdd(&hdr[kFdSumMsgs], 1u);
-    mc.xxh[m] = xxh;
-    mc.first[m] = base;
-    mc.nb[m] = nb;
-    mc.route[m] = chain ? kRouteLinkedNsFast : kRouteNoSizeFast;
+  if (!sized && !nosize_fast) {
+    mc.route[m] = kRouteNoSize;
     return;
   }
-  // fast route: every block but the last is full
+  // the fast routes.  Sized: every block but the last is full.  No content
+  // size: the blocks' lengths are unknown until the length pass.
   mc.route[m] = kRouteRejected;
-  const u32 bs = h.block_max;
-  const u32 bsum = (h.flg & lz4f::kFlgBlockSum) ? 4 : 0;
-  const u32 nb = (u32)((h.size + bs - 1) / bs);
-  u64 ip = h.len, need = 0;
-  for (u32 k = 0; k < nb; ++k) {
-    if (n - ip < 4) return;
-    const u32 word = lz4f::rd32(ib + ip);
-    const u32 sz = word & ~lz4f::kRawBit;
-    ip += 4;
-    if (sz == 0 || sz > bs || n - ip < (u64)sz + bsum) return;
-    const u64 exp = h.size - (u64)k * bs < bs ? h.size - (u64)k * bs : bs;
-    if (word & lz4f::kRawBit) {
-      if (sz != exp) return;
-    } else {
-      need += dec_slot(sz);
-    }
-    ip += sz + bsum;
-  }
-  if (n - ip < 4 || lz4f::rd32(ib + ip) != 0) return;
-  ip += 4;
-  if (h.flg & lz4f::kFlgSum) {
-    if (n - ip < 4) return;
-    mc.xxh[m] = lz4f::rd32(ib + ip);
-    ip += 4;
-  }
-  if (ip != n) return;
-  const u32 base = atomicAdd(&hdr[kFdBlocks], nb);
-  u64 sb = atomicAdd(reinterpret_cast<unsigned long long*>(hdr + kFdStage), (unsigned long long)need);
-  if ((u64)base + nb > nb_cap || sb + need > stage_cap) return;
-  const u64 io = in_off[m], oo = out_off[m];
-  ip = h.len;
-  for (u32 k = 0; k < nb; ++k) {
-    const u32 e = base + k;
-    const u32 word = lz4f::rd32(ib + ip);
-    const u32 sz = word & ~lz4f::kRawBit;
-    const bool raw = word & lz4f::kRawBit;
-    ip += 4;
-    const u32 exp = (u32)(h.size - (u64)k * bs < bs ? h.size - (u64)k * bs : bs);
-    c.src_off[e] = io + ip;
-    c.src_len[e] = sz;
-    c.out_off[e] = oo + (u64)k * bs;
-    c.out_cap[e] = exp;
-    c.flags[e] = kBlkListed | (raw ? kBlkRaw : 0) | (bsum ? kBlkSum : 0) |
-                 (chain ? kBlkChained | (lz4f::linked_prefix((u64)k * bs) << kBlkPrefixShift) : 0);
-    if (!raw) {
-      c.in_off[e] = stage_off + sb;
-      c.in_len[e] = (u32)varint32_len(exp) + sz;
-      sb += dec_slot(sz);
-    }
-    ip += sz + bsum;
-  }
-  if (bsum) atomicAdd(&hdr[kFdSumBlocks], nb);
-  if (h.flg & lz4f::kFlgSum) atomicAdd(&hdr[kFdSumMsgs], 1u);
-  mc.first[m] = base;
-  mc.nb[m] = nb;
-  mc.route[m] = chain ? kRouteLinkedFast : kRouteFast;
+  u32 nb, xxh, base;
+  u64 need = 0, sb;  // (staging bytes for the compressed blocks)
+  const auto each = [&need](const lz4f::Block& b) { need += b.raw ? 0 : dec_slot(b.size); };
+  if (!lz4f::check_blocks(ib, n, h, lz4f::BlockRules{false, sized}, each, &nb, &xxh)) return;
+  const u32 route = sized ? (chain ? kRouteLinkedFast : kRouteFast) : (chain ? kRouteLinkedNsFast : kRouteNoSizeFast);
+  if (!claim_blocks(hdr, mc, m, h, nb, xxh, route, nb_cap, true, need, stage_cap, &base, &sb)) return;
+  list_blocks(ib, n, h, in_off[m], out_off[m], nb, base, stage_off + sb, chain, c);
 }
 
 // ---- the length pass (frames without a content size)
@@ -600,7 +316,7 @@ __global__ __launch_bounds__(256) void lz4f_place_kernel(u32 n_msgs, const u64* 
 // fsg_lz4f_decoded_lengths_batch, one lane per message: the stated content
 // size, or the frame's blocks listed for the length pass (linked or not:
 // lengths do not depend on linking).  A frame whose entries do not fit is
-// walked here.
+// walked here, by the host codec's own function.
 __global__ __launch_bounds__(64) void lz4f_length_index_kernel(const u8* __restrict__ in,
                                                              const u64* __restrict__ in_off,
                                                              const u32* __restrict__ in_len, u32 n_msgs,
@@ -622,36 +338,20 @@ __global__ __launch_bounds__(64) void lz4f_length_index_kernel(const u8* __restr
     lengths[m] = h.size;
     return;
   }
-  u32 nb, xxh;
-  u64 need;
-  if (!walk_blocks(ib, n, h, true, &nb, &need, &xxh)) {
+  u32 nb, xxh, base;
+  u64 sb;
+  if (!lz4f::check_blocks(ib, n, h, lz4f::BlockRules{true, false}, [](const lz4f::Block&) {}, &nb, &xxh)) {
     status[m] = kCorrupt;
     return;
   }
   if (nb == 0) return;
-  const u32 base = atomicAdd(&hdr[kFdBlocks], nb);
-  if ((u64)base + nb <= nb_cap) {
-    list_unknown(ib, h, in_off[m], nb, base, 0, c);
-    mc.first[m] = base;
-    mc.nb[m] = nb;
-    mc.route[m] = kRouteNoSizeFast;
+  if (claim_blocks(hdr, mc, m, h, nb, xxh, kRouteNoSizeFast, nb_cap, false, 0, 0, &base, &sb)) {
+    list_blocks(ib, n, h, in_off[m], 0, nb, base, 0, false, c);
     return;
   }
-  const u32 bsum = (h.flg & lz4f::kFlgBlockSum) ? 4 : 0;
-  u64 ip = h.len, total = 0;
-  for (u32 k = 0; k < nb; ++k) {
-    const u32 word = lz4f::rd32(ib + ip);
-    const u32 sz = word & ~lz4f::kRawBit;
-    ip += 4;
-    u64 len = sz;
-    if (!(word & lz4f::kRawBit) && !lz4f::block_length(ib + ip, sz, h.block_max, &len)) {
-      status[m] = kCorrupt;
-      return;
-    }
-    total += len;
-    ip += sz + bsum;
-  }
-  lengths[m] = total;
+  u64 total;
+  if (lz4f::blocks_decoded_length(ib, n, h, &total)) lengths[m] = total;
+  else status[m] = kCorrupt;
 }
 
 // One wave per listed block: a compressed block becomes a body of the block
@@ -769,8 +469,9 @@ __global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ 
   // a linked frame whose chain did not run to its end: the serial decoder
   if (route == kRouteLinkedFast || route == kRouteLinkedNsFast) route = kRouteRejected;
   const bool lk = route == kRouteLinkedOk || route == kRouteLinkedNsOk;
-  if (route == kRouteFast || route == kRouteLinkedOk) {
-    const u32 first = mc.first[m], nb = mc.nb[m];
+  const bool sized = route == kRouteFast || route == kRouteLinkedOk;
+  if (sized || route == kRouteNoSizeFast || route == kRouteLinkedNsOk) {
+    const u32 first = mc.first[m], nb = mc.nb[m], last = first + nb - 1;
     bool ok = true;
     for (u32 k = 0; k < nb && ok; ++k) ok = !(c.flags[first + k] & kBlkFailed);
     lz4f::Header h;
@@ -780,29 +481,11 @@ __global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ 
       sums = 1;
     }
     if (ok) {
-      out_len[m] = (u32)h.size;
+      // without a content size the blocks lie end to end from the slot's
+      // start: decoded exactly the lengths the walk found
+      out_len[m] = sized ? (u32)h.size : (u32)(c.out_off[last] + c.out_cap[last] - out_off[m]);
       status[m] = kOk;
-      blocks = nb;
-    } else {
-      route = kRouteRejected;
-    }
-  } else if (route == kRouteNoSizeFast || route == kRouteLinkedNsOk) {
-    // the blocks lie end to end from the slot's start: decoded exactly the
-    // lengths the walk found, and the checksum over them
-    const u32 first = mc.first[m], nb = mc.nb[m], last = first + nb - 1;
-    bool ok = true;
-    for (u32 k = 0; k < nb && ok; ++k) ok = !(c.flags[first + k] & kBlkFailed);
-    const u32 total = (u32)(c.out_off[last] + c.out_cap[last] - out_off[m]);
-    lz4f::Header h;
-    lz4f::parse_header(ib, in_len[m], &h);
-    if (ok && (h.flg & lz4f::kFlgSum)) {
-      ok = mc.xxh[m] == 0;
-      sums = 1;
-    }
-    if (ok) {
-      out_len[m] = total;
-      status[m] = kOk;
-      ns_blocks = nb;
+      (sized ? blocks : ns_blocks) = nb;
     } else {
       route = kRouteRejected;
     }
@@ -831,40 +514,18 @@ __global__ __launch_bounds__(64) void lz4f_finish_kernel(const u8* __restrict__ 
   }
 }
 
-// ---- the columns in a workspace (offsets and sizes: lz4_frame_plan.h)
-MsgCols msg_cols(u8* w, u32 n_msgs) {
-  MsgCols mc;
-  const u64 lb = lz4f_list_bytes(n_msgs);
-  mc.route = reinterpret_cast<u32*>(w);
-  mc.first = reinterpret_cast<u32*>(w + lb);
-  mc.nb = reinterpret_cast<u32*>(w + 2 * lb);
-  mc.xxh = reinterpret_cast<u32*>(w + 3 * lb);
-  return mc;
-}
-BlockCols block_cols(u8* w, u64 nb) {
-  const Lz4fBlockColOff o = lz4f_block_col_off(nb);
-  BlockCols c;
-  c.in_off = reinterpret_cast<u64*>(w + o.in_off);
-  c.out_off = reinterpret_cast<u64*>(w + o.out_off);
-  c.src_off = reinterpret_cast<u64*>(w + o.src_off);
-  c.in_len = reinterpret_cast<u32*>(w + o.in_len);
-  c.out_cap = reinterpret_cast<u32*>(w + o.out_cap);
-  c.out_len = reinterpret_cast<u32*>(w + o.out_len);
-  c.status = reinterpret_cast<i32*>(w + o.status);
-  c.src_len = reinterpret_cast<u32*>(w + o.src_len);
-  c.flags = reinterpret_cast<u32*>(w + o.flags);
-  return c;
+// the length pass on the claimed entries: lanes, then the listed large blocks
+hipError_t launch_length_pass(const u8* in, u32* hdr, const BlockCols& c, const Lz4fDecodePlan& plan,
+                              hipStream_t stream) {
+  lz4f_length_lane_kernel<<<plan.length_lane_grid, 64, 0, stream>>>(in, hdr, c, plan.w.nb_cap, plan.length_wave_min);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  lz4f_length_wave_kernel<<<plan.length_wave_grid, kLenWaves * 64, 0, stream>>>(in, hdr, c);
+  return hipGetLastError();
 }
 
 }  // namespace
 
-void lz4f_encode_header_counts(const void* header, Lz4fEncodeHeaderCounts* c) {
-  u32 ctr[8];
-  __builtin_memcpy(ctr, header, sizeof(ctr));
-  c->blocks = ctr[kFcListed];
-  c->raw_blocks = ctr[kFcRaw];
-  c->overflow_messages = ctr[kFcOverflow];
-}
 void lz4f_decode_header_counts(const void* header, Lz4fDecodeHeaderCounts* c) {
   u32 ctr[kFdLkBlocks + 1];
   __builtin_memcpy(ctr, header, sizeof(ctr));
@@ -883,64 +544,12 @@ void lz4f_decode_header_counts(const void* header, Lz4fDecodeHeaderCounts* c) {
   c->inner_fallback = ctr[kFdInner];
 }
 
-// every size and decision from lz4f_encode_plan (lz4_frame_plan.h)
-hipError_t launch_lz4f_encode(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u8* out,
-                              const u64* out_off, u32* out_len, i32* status, u32 id, u32 flags, void* ws,
-                              hipStream_t stream, const Lz4fEncodePlan& plan) {
-  if (n_msgs == 0) return hipSuccess;
-  if (!plan.valid) return hipErrorInvalidValue;
-  const Lz4fLayout& p = plan.w;
-  u8* const w = static_cast<u8*>(ws);
-  u32* const hdr = reinterpret_cast<u32*>(w);
-  const MsgCols mc = msg_cols(w + p.off_msg, n_msgs);
-  const BlockCols c = block_cols(w + p.off_blk, p.nb_cap);
-  const u32 bs = lz4f::block_bytes(id);
-  hipError_t e = hipMemsetAsync(w, 0, kLz4fHead, stream);
-  if (e != hipSuccess) return e;
-  lz4f_prefill_kernel<<<plan.prefill_grid, 256, 0, stream>>>(c, p.nb_cap, p.off_dummy);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  lz4f_plan_kernel<<<plan.plan_grid, 64, 0, stream>>>(in_off, in_len, n_msgs, bs, hdr, mc, c, p.nb_cap, p.off_stage,
-                                                     p.stage_cap);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  // the block encoders on the block columns, with their own routing
-  e = launch_lz4_encode(in, c.in_off, c.in_len, p.nb_cap, w, c.out_off, c.out_len, c.status, w + p.off_inner, stream,
-                        plan.inner);
-  if (e != hipSuccess) return e;
-  // the checksum kernel: the messages, and the entries' bytes as stored
-  if (flags & lz4f::kOptContentSum) {
-    if ((e = launch_xxh_quads(BodyUnits{in, in_off, in_len, 0u, mc.xxh}, n_msgs, stream)) != hipSuccess) return e;
-  }
-  if (flags & lz4f::kOptBlockSums) {
-    if ((e = launch_xxh_quads(StoredUnits{in, w, c}, p.nb_cap, stream)) != hipSuccess) return e;
-  }
-  lz4f_assemble_kernel<<<plan.assemble_grid, 64, 0, stream>>>(in, in_len, out, out_off, out_len, status, id, flags, hdr,
-                                                             mc, c, w);
-  return hipGetLastError();
-}
-
-hipError_t launch_lz4f_xxh32(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u32 seed, u32* xxh,
-                             hipStream_t stream) {
-  return launch_xxh_quads(BodyUnits{in, in_off, in_len, seed, xxh}, n_msgs, stream);
-}
-
 hipError_t launch_lz4f_content_sizes(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* sizes,
                                      i32* status, hipStream_t stream) {
   if (n_msgs == 0) return hipSuccess;
   lz4f_sizes_kernel<<<(n_msgs + 63) / 64, 64, 0, stream>>>(in, in_off, in_len, n_msgs, sizes, status);
   return hipGetLastError();
 }
-
-namespace {
-// the length pass on the claimed entries: lanes, then the listed large blocks
-hipError_t launch_length_pass(const u8* in, u32* hdr, const BlockCols& c, const Lz4fDecodePlan& plan,
-                              hipStream_t stream) {
-  lz4f_length_lane_kernel<<<plan.length_lane_grid, 64, 0, stream>>>(in, hdr, c, plan.w.nb_cap, plan.length_wave_min);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  lz4f_length_wave_kernel<<<plan.length_wave_grid, kLenWaves * 64, 0, stream>>>(in, hdr, c);
-  return hipGetLastError();
-}
-}  // namespace
 
 // every size and decision of the two launches below from lz4f_decode_plan (lz4_frame_plan.h)
 hipError_t launch_lz4f_decoded_lengths(const u8* in, const u64* in_off, const u32* in_len, u32 n_msgs, u64* lengths,

@@ -1,8 +1,10 @@
 // lz4_frame_format.h -- the LZ4 frame format (1.6.x) in plain C++: XXH32, the
-// descriptor, and the serial frame decoder.  One text for three users: the
-// device code (lz4_frame.hip, where LZ4F_HD is __host__ __device__), the host
-// codec (host/lz4_cpu.cc, compiled by g++) and tests/cpp/lz4f_host_check.hip,
-// which runs the decoder on the CPU under AddressSanitizer.
+// descriptor, the walk over a frame's size words and the serial frame decoder.
+// One text for three users: the device code (lz4_frame_encode.hip,
+// lz4_frame_decode.hip, where LZ4F_HD is __host__ __device__), the host codec
+// (host/lz4_cpu.cc, compiled by g++) and the stand-alone programs that run it
+// on the CPU under AddressSanitizer (tests/cpp/lz4f_host_check.hip: the
+// decoder; tests/cpp/test_lz4f_walk.cc: the walk under every reader's rules).
 // include/flare_lz4_gpu.h states the rules ("LZ4 frames").
 #pragma once
 
@@ -262,6 +264,101 @@ LZ4F_HD bool block_decode(const uint8_t* src, uint32_t n, uint8_t* dst, uint32_t
 // it, as far as an offset goes.
 LZ4F_HD uint32_t linked_prefix(uint64_t produced) { return produced < 65535 ? (uint32_t)produced : 65535u; }
 
+// ---- the walk over a frame's size words: the one reader of the block
+// structure.  A block's stored bytes lie at in + at; its checksum word, when
+// the descriptor flags block checksums, right after them.
+struct Block {
+  uint64_t at;
+  uint32_t size;
+  bool raw;
+};
+struct BlockWalk {
+  const uint8_t* in;
+  uint64_t n, ip;
+  uint32_t block_max, flg;
+};
+enum WalkStep { kWalkBlock, kWalkEnd, kWalkBad };
+
+LZ4F_HD BlockWalk begin_blocks(const uint8_t* in, uint64_t n, const Header& h) {
+  return BlockWalk{in, n, h.len, h.block_max, h.flg};
+}
+LZ4F_HD uint32_t block_sum_bytes(uint32_t flg) { return (flg & kFlgBlockSum) ? 4 : 0; }
+
+// kWalkBad: no size word left, a size above the block maximum, or the stored
+// bytes with their checksum word not inside the input.  kWalkEnd: the end mark.
+// kChecked = false: nothing tested, no branch at the load (a second pass over counted blocks).
+template <bool kChecked = true>
+LZ4F_HD WalkStep next_block(BlockWalk* w, Block* b) {
+  if (kChecked && w->n - w->ip < 4) return kWalkBad;
+  const uint32_t word = rd32(w->in + w->ip);
+  w->ip += 4;
+  if (kChecked && word == 0) return kWalkEnd;
+  b->at = w->ip;
+  b->size = word & ~kRawBit;
+  b->raw = word & kRawBit;
+  const uint64_t stored = (uint64_t)b->size + block_sum_bytes(w->flg);
+  if (kChecked && (b->size > w->block_max || w->n - w->ip < stored)) return kWalkBad;
+  w->ip += stored;
+  return kWalkBlock;
+}
+
+// After kWalkEnd: the content checksum word when the descriptor flags one
+// (*stated_xxh, else 0; not verified), and nothing after the frame.
+LZ4F_HD bool end_frame(BlockWalk* w, uint32_t* stated_xxh) {
+  *stated_xxh = 0;
+  if (w->flg & kFlgSum) {
+    if (w->n - w->ip < 4) return false;
+    *stated_xxh = rd32(w->in + w->ip);
+    w->ip += 4;
+  }
+  return w->ip == w->n;
+}
+
+// What a block-parallel reader asks of the structure beyond the walk's own
+// rules.  (A block of size 0 is a raw one: the word 0 is the end mark.)
+struct BlockRules {
+  bool zero_raw;  // an empty raw block is accepted (the lengths call, as the serial decoder does)
+  bool sized;     // the sized fast route: ceil(content size / block maximum) blocks, a raw one as long as its place
+};
+
+// The whole structure of a frame by `rules`: each(block) for every block in
+// order, then *nb blocks and *stated_xxh (end_frame).  false: rejected.
+template <typename Each>
+LZ4F_HD bool check_blocks(const uint8_t* in, uint64_t n, const Header& h, BlockRules rules, Each each, uint32_t* nb,
+                          uint32_t* stated_xxh) {
+  const uint64_t bs = h.block_max;
+  const uint32_t want = rules.sized ? (uint32_t)((h.size + bs - 1) / bs) : 0xFFFFFFFFu;
+  BlockWalk w = begin_blocks(in, n, h);
+  Block b;
+  uint32_t k = 0;
+  WalkStep s;
+  for (; (s = next_block(&w, &b)) == kWalkBlock; ++k) {
+    if (k == want) return false;
+    if (b.size == 0 && !rules.zero_raw) return false;
+    if (rules.sized && b.raw && b.size != (h.size - k * bs < bs ? h.size - k * bs : bs)) return false;
+    each(b);
+  }
+  if (s != kWalkEnd || (rules.sized && k != want)) return false;
+  *nb = k;
+  return end_frame(&w, stated_xxh);
+}
+
+// The decoded length of a frame without a content size, from its blocks'
+// sequences: the walk's rules, block_length against the block maximum, no
+// checksum verified.  false: the frame is corrupt.
+LZ4F_HD bool blocks_decoded_length(const uint8_t* in, uint64_t n, const Header& h, uint64_t* total) {
+  BlockWalk w = begin_blocks(in, n, h);
+  Block b;
+  WalkStep s;
+  uint32_t xxh;
+  for (*total = 0; (s = next_block(&w, &b)) == kWalkBlock;) {
+    uint64_t len = b.size;
+    if (!b.raw && !block_length(in + b.at, b.size, h.block_max, &len)) return false;
+    *total += len;
+  }
+  return s == kWalkEnd && end_frame(&w, &xxh);
+}
+
 // ---- the serial frame decoder: one frame per body, every write below
 // out + cap.  *out_len: the decoded length on kStOk, min(content size, 2^32-1)
 // on kStSlotTooSmall, else 0.  *checksums (may be null): block and content
@@ -276,40 +373,35 @@ LZ4F_HD int32_t decode_frame(const uint8_t* in, uint64_t n, uint8_t* out, uint64
     return kStSlotTooSmall;
   }
   const uint64_t limit = h.size != kNoSize ? h.size : cap;
-  const uint32_t bsum = (h.flg & kFlgBlockSum) ? 4 : 0;
-  uint64_t ip = h.len, op = 0;
-  uint32_t sums = 0;
-  for (;;) {
-    if (n - ip < 4) return kStCorrupt;
-    const uint32_t word = rd32(in + ip);
-    ip += 4;
-    if (word == 0) break;
-    const uint32_t size = word & ~kRawBit;
-    if (size > h.block_max || n - ip < (uint64_t)size + bsum) return kStCorrupt;
-    const uint8_t* blk = in + ip;
-    ip += size + bsum;
-    if (bsum) {
-      if (xxh32(blk, size) != rd32(blk + size)) return kStCorrupt;
+  BlockWalk w = begin_blocks(in, n, h);
+  Block b;
+  WalkStep s;
+  uint64_t op = 0;
+  uint32_t sums = 0, stated;
+  while ((s = next_block(&w, &b)) == kWalkBlock) {
+    const uint8_t* blk = in + b.at;
+    if (h.flg & kFlgBlockSum) {
+      if (xxh32(blk, b.size) != rd32(blk + b.size)) return kStCorrupt;
       ++sums;
     }
-    if (word & kRawBit) {
-      if (size > limit - op) return kStCorrupt;
-      copy_bytes(out + op, blk, size);
-      op += size;
+    if (b.raw) {
+      if (b.size > limit - op) return kStCorrupt;
+      copy_bytes(out + op, blk, b.size);
+      op += b.size;
       continue;
     }
     const uint64_t room = limit - op < h.block_max ? limit - op : h.block_max;
     uint64_t len;
-    if (!block_length(blk, size, room, &len)) return kStCorrupt;
-    if (!block_decode(blk, size, out + op, (uint32_t)len, (h.flg & kFlgIndep) ? 0 : op)) return kStCorrupt;
+    if (!block_length(blk, b.size, room, &len)) return kStCorrupt;
+    if (!block_decode(blk, b.size, out + op, (uint32_t)len, (h.flg & kFlgIndep) ? 0 : op)) return kStCorrupt;
     op += len;
   }
+  if (s != kWalkEnd || !end_frame(&w, &stated)) return kStCorrupt;
   if (h.flg & kFlgSum) {
-    if (n - ip < 4 || xxh32(out, op) != rd32(in + ip)) return kStCorrupt;
-    ip += 4;
+    if (xxh32(out, op) != stated) return kStCorrupt;
     ++sums;
   }
-  if (ip != n || (h.size != kNoSize && op != h.size)) return kStCorrupt;
+  if (h.size != kNoSize && op != h.size) return kStCorrupt;
   *out_len = (uint32_t)op;
   if (checksums) *checksums = sums;
   return kStOk;

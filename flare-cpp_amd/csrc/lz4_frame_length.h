@@ -1,7 +1,7 @@
 // lz4_frame_length.h -- the decoded length of one LZ4 block by a whole wave:
 // lz4f::block_length (lz4_frame_format.h) for a block of a frame that states
 // no content size, where the sequences are the only place a block's length is
-// written.  Included by lz4_frame.hip alone.  The shape is lz4_walk_big's
+// written.  Included by lz4_frame_decode.hip alone.  The shape is lz4_walk_big's
 // (lz4_decode2.hip), the code is its own: nothing here needs offsets, output
 // positions per sequence or the block decoder's end rules, only lengths.
 //

@@ -1,4 +1,5 @@
-// lz4_frame_plan.h -- LZ4 frames (lz4_frame.hip): the workspace layouts and
+// lz4_frame_plan.h -- LZ4 frames (lz4_frame_encode.hip,
+// lz4_frame_decode.hip): the workspace layouts and
 // everything a launch decides before its first kernel, the plans of the inner
 // block launches included, as plain host arithmetic.  The path reports read
 // the same structs.  No HIP include: tests/cpp/test_lz4_plan.cc checks it on
@@ -10,7 +11,7 @@
 
 namespace fsg {
 
-constexpr u64 kLz4fHead = 256;  // the workspace header: counters (lz4_frame.hip, kFc* / kFd*)
+constexpr u64 kLz4fHead = 256;  // the workspace header: counters (kFc*, kFd* of lz4_frame_encode.hip, lz4_frame_decode.hip)
 
 LZ4F_HD u64 round_up(u64 v, u64 a) { return (v + a - 1) / a * a; }
 

@@ -1,5 +1,6 @@
 // lz4f_xxh.h -- XXH32 of many byte ranges at once, a quad of lanes per range:
-// the checksum kernel of the LZ4 frame calls (lz4_frame.hip) and of
+// the checksum kernel of the LZ4 frame calls (lz4_frame_encode.hip,
+// lz4_frame_decode.hip) and of
 // fsg_lz4f_xxh32_batch.  lz4f::xxh32 (lz4_frame_format.h) stays the serial
 // text; this gives the same words.
 //

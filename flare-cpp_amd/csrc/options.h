@@ -39,7 +39,7 @@ enum Opt : int {
   // LZ4 compress (lz4_encode_wave.hip)
   kOptLz4EncodeWaveMin,   // -1 automatic; bodies of at least this many bytes take the wave encoder (>= 0xFFFFFFFF: none)
   kOptLz4EncodeWavePerCu, // wave encoder waves per CU (0 = as many as LDS holds)
-  // LZ4 frames (lz4_frame.hip)
+  // LZ4 frames (lz4_frame_encode.hip, lz4_frame_decode.hip)
   kOptLz4fForceSerial,    // 1: every frame on the serial decoder
   kOptLz4fBlockWaveMin,   // the block encode's wave threshold (as lz4_encode_wave_min; -1: its automatic rule)
   kOptLz4fNosizeFast,     // 1: frames with independent blocks and no content size on the block decoders

@@ -269,28 +269,10 @@ uint64_t FrameDecodedLength(const uint8_t* in, size_t n, int* status) {
   *status = lz4f::parse_header(in, n, &h);
   if (*status != lz4f::kStOk) return 0;
   if (h.size != lz4f::kNoSize) return h.size;
+  uint64_t total;
+  if (lz4f::blocks_decoded_length(in, n, h, &total)) return total;
   *status = lz4f::kStCorrupt;
-  const uint32_t bsum = (h.flg & lz4f::kFlgBlockSum) ? 4 : 0;
-  uint64_t ip = h.len, total = 0;
-  for (;;) {
-    if (n - ip < 4) return 0;
-    const uint32_t word = lz4f::rd32(in + ip);
-    ip += 4;
-    if (word == 0) break;
-    const uint32_t size = word & ~lz4f::kRawBit;
-    if (size > h.block_max || n - ip < static_cast<uint64_t>(size) + bsum) return 0;
-    uint64_t len = size;
-    if (!(word & lz4f::kRawBit) && !lz4f::block_length(in + ip, size, h.block_max, &len)) return 0;
-    total += len;
-    ip += size + bsum;
-  }
-  if (h.flg & lz4f::kFlgSum) {
-    if (n - ip < 4) return 0;
-    ip += 4;
-  }
-  if (ip != n) return 0;
-  *status = lz4f::kStOk;
-  return total;
+  return 0;
 }
 
 }  // namespace flare::lz4::cpu

@@ -1,5 +1,6 @@
 """GPU tests of the compress flags of the LZ4 frame calls (content checksum,
-block checksums, no content size: flare-cpp_amd/csrc/lz4_frame.hip) and of the
+block checksums, no content size: flare-cpp_amd/csrc/lz4_frame_encode.hip) and
+of the
 checksum kernel behind every XXH32 of those calls (csrc/lz4f_xxh.h: a quad of
 lanes per unit), alone through fsg_lz4f_xxh32_batch and inside compress and
 decompress, through the C ABI.  Expected checksums are tests/lz4f_ref.xxh32,

@@ -1,4 +1,5 @@
-"""GPU parity of the LZ4 frame calls (flare-cpp_amd/csrc/lz4_frame.hip) through
+"""GPU parity of the LZ4 frame calls (flare-cpp_amd/csrc/lz4_frame_encode.hip,
+lz4_frame_decode.hip) through
 the C ABI (include/flare_lz4_gpu.h, "LZ4 frames"): frames byte-equal to the
 liblz4 fixtures and to the frame oracle (tests/lz4f_ref.py), every decode
 verdict and accepted byte equal to the oracle's on the fast and on the serial

@@ -1,5 +1,5 @@
 """GPU tests of the fast route for LZ4 frames with linked blocks (option
-lz4f_linked_fast; flare-cpp_amd/csrc/lz4_frame.hip, and the prefix forms and
+lz4f_linked_fast; flare-cpp_amd/csrc/lz4_frame_decode.hip, and the prefix forms and
 lz4_exec_chain_kernel of lz4_decode2.hip), through the C ABI.  Expected
 statuses, lengths and bytes are the frame oracle's (tests/lz4f_ref.py,
 decode_frame); the frames come from tests/lz4f_linked_cases.py and

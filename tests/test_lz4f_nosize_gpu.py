@@ -1,5 +1,5 @@
 """GPU tests of the block-parallel route for LZ4 frames without a content size
-(option lz4f_nosize_fast; flare-cpp_amd/csrc/lz4_frame.hip, lz4_frame_length.h)
+(option lz4f_nosize_fast; flare-cpp_amd/csrc/lz4_frame_decode.hip, lz4_frame_length.h)
 and of fsg_lz4f_decoded_lengths_batch, through the C ABI.  Expected statuses,
 lengths and bytes are the frame oracle's (tests/lz4f_ref.py: decode_frame,
 block_length); the frames come from tests/lz4f_nosize_cases.py.  Every
